@@ -11,7 +11,15 @@ re-parses every file; nothing is cached across steps.  Enrichment
 is disabled by default (BASELINE: "Indexing throughput with enrichment
 disabled"); ``--enrich fake`` adds Phase 2/3 with the offline fake backend.
 
-``extra.enrichLocal`` (GPU present, ``--enrich-local-classes`` > 0): after
+A plain run sets up, warms up, times ``--steps`` analyses and prints the
+result line (``ms_per_step`` = milliseconds per timed step); with
+``--dump-outputs DIR`` it also writes what the last timed step computed as
+``DIR/<name>.npy`` (see ``_dump_outputs``; same arguments, same inputs, so two
+builds compare output for output).  Everything else -- query latencies, the
+TS / Go indexing runs, the remote-repository path and the local-model
+enrichment runs below -- is measured only with ``--full``.
+
+``extra.enrichLocal`` (``--full``, GPU present, ``--enrich-local-classes`` > 0): after
 the headline, each rank runs a real ``analyze_project`` of a
 ``--enrich-local-classes``-class repository with the optional MI355X
 enrichment backend in the service configuration -- one worker process per
@@ -58,6 +66,13 @@ def parse_args(argv=None):
     ap.add_argument("--enrich", default="none", choices=["none", "fake", "local"])
     ap.add_argument("--queries", type=int, default=200, help="graph_query / stack-trace latency samples")
     ap.add_argument("--workdir", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every secondary measurement (extra.graphQueryMs, "
+                         "stackTrace20Ms, tsIndex, goIndex, remotePath, enrichLocal*); a plain run measures "
+                         "the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (rank 0's analysis result and published "
+                         "graph) as DIR/<name>.npy")
     ap.add_argument("--enrich-local-classes", type=int, default=256,
                     help="classes of the end-to-end local-model enrichment run (extra.enrichLocal; 0 = skip)")
     ap.add_argument("--enrich-local-kv", default="fp8", choices=["bf16", "fp8"])
@@ -77,7 +92,10 @@ def parse_args(argv=None):
     ap.add_argument("--small-project-classes", type=int, default=33,
                     help="classes of the latency-bound enrichment run (extra.enrichLocal*.smallProject: what "
                          "each of 8 GPUs gets when one 257-class project is dealt over 8; 0 = skip)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 EXTRA_KEYS = {"dmcp-coder-1b": "enrichLocal", "llama3.2-1b-code": "enrichLocalLlama"}
@@ -358,9 +376,63 @@ def _remote_path(args, work, repo, threads):
         app.close()
 
 
+DUMP_MAX_BYTES = (64 << 20) - 4096  # all files of one --dump-outputs together (room for the .npy headers)
+
+
+def _capped(arr, budget: int):
+    """``arr`` itself, or a fixed (seeded) sample of its rows that fits ``budget`` bytes."""
+    import numpy as np
+    row = max(1, arr.nbytes // max(1, len(arr)))
+    if arr.nbytes <= budget:
+        return arr
+    keep = np.sort(np.random.default_rng(0).choice(len(arr), size=max(1, budget // row), replace=False))
+    return arr[keep]
+
+
+def _dump_outputs(out_dir: str, app, result) -> None:
+    """--dump-outputs: what a caller of the timed ``analyze_project`` holds
+    after the last step -- the AnalysisResult's counts and the graph it
+    published to the cache -- as float arrays that two builds can compare.
+    Row ids (fresh UUIDv7s per analysis) are left out; identifiers are sorted,
+    so the arrays do not depend on container iteration order.
+
+    * ``analysis.npy``     float64 [classesAnalyzed, endpointsFound, nodes, edges, entryPoints]
+    * ``class_table.npy``  float32 (nodes, 5), rows by sorted identifier:
+      [dependencies, dependents, methods, endpoint methods, is entry point]
+    * ``graph_json.npy``   float32, the UTF-8 bytes of the graph's canonical JSON
+      (keys and edge lists sorted, class ids removed)
+    """
+    import numpy as np
+    graph = app.cache.get_graph(result.project_id)
+    if graph is None:
+        raise RuntimeError("--dump-outputs: the last timed step published no graph")
+    doc = graph.to_dict()
+    for node in doc["nodes"].values():
+        node.pop("classId", None)
+    doc["edges"] = {k: sorted(v) for k, v in doc["edges"].items()}
+    doc["entryPoints"] = sorted(doc["entryPoints"])
+    idents = sorted(doc["nodes"])
+    table = np.zeros((len(idents), 5), dtype=np.float32)
+    for i, ident in enumerate(idents):
+        methods = doc["methodInfo"].get(ident, ())
+        table[i] = (len(graph.dependencies(ident)), len(graph.dependents(ident)), len(methods),
+                    sum(1 for m in methods if m.get("httpMethod") is not None), float(graph.is_entry_point(ident)))
+    counts = np.array([result.classes_analyzed, result.endpoints_found, graph.node_count(), graph.edge_count(),
+                       graph.entry_point_count()], dtype=np.float64)
+    text = json.dumps(doc, sort_keys=True, separators=(",", ":"), ensure_ascii=False).encode("utf-8")
+    raw = np.frombuffer(text, dtype=np.uint8).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_MAX_BYTES - counts.nbytes
+    table = _capped(table, budget // 4)
+    raw = _capped(raw, budget - table.nbytes)
+    for name, arr in (("analysis", counts), ("class_table", table), ("graph_json", raw)):
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def main(argv=None) -> int:
     args = parse_args(argv)
-    pools = _spawn_enrich_pools(args) if args.enrich == "none" else {}  # before anything touches HIP
+    # the enrichment workers belong to the --full measurements; before anything touches HIP
+    pools = _spawn_enrich_pools(args) if args.full and args.enrich == "none" else {}
     from dmcp.parallel.dist import init_from_env
     ctx = init_from_env()
     rank, world = ctx.rank, ctx.world
@@ -402,10 +474,13 @@ def main(argv=None) -> int:
         # whole-job aggregate: MAX elapsed over ranks, SUM of classes
         elapsed = ctx.max(elapsed)[0]
         total_classes = int(ctx.sum(float(n_classes))[0])
-        # query latencies on the indexed graph (BASELINE configs 3/4)
+        if rank == 0 and args.dump_outputs:
+            _dump_outputs(args.dump_outputs, app, r)
         extra = {"phaseMsPerStep": {k: round(v / max(1, args.steps), 2) for k, v in stats_acc.items()},
                  "classesPerRepo": r.classes_analyzed, "parserThreadsPerRank": threads}
-        if rank == 0 and args.queries > 0:
+        # everything from here to the result line is a --full measurement
+        # query latencies on the indexed graph (BASELINE configs 3/4)
+        if args.full and rank == 0 and args.queries > 0:
             project = f"shop{rank}"
             qs = [f"{project}:endpoints", f"{project}:classes", f"{project}:OrderService:methods:+logic",
                   f"{project}:UserController:dependencies", f"{project}:entrypoints:+logic",
@@ -426,14 +501,14 @@ def main(argv=None) -> int:
             extra["graphQueryMs"] = {"p50": round(lat[len(lat) // 2], 3), "p99": round(lat[int(len(lat) * 0.99) - 1], 3)}
             extra["stackTrace20Ms"] = {"p50": round(st_lat[len(st_lat) // 2], 3),
                                        "p99": round(st_lat[max(0, int(len(st_lat) * 0.99) - 1)], 3)}
-        for kind in (("ts", "go") if rank == 0 and args.lang_files > 0 else ()):
+        for kind in (("ts", "go") if args.full and rank == 0 and args.lang_files > 0 else ()):
             key = "tsIndex" if kind == "ts" else "goIndex"
             try:
                 extra[key] = _lang_index(kind, args, work, threads)
             except Exception as e:
                 logging.getLogger("bench").exception("%s failed", key)
                 extra[key] = {"error": repr(e)[:300]}
-        if rank == 0 and args.remote_steps > 0:
+        if args.full and rank == 0 and args.remote_steps > 0:
             try:
                 extra["remotePath"] = _remote_path(args, work, repo, threads)
             except Exception as e:
@@ -442,7 +517,7 @@ def main(argv=None) -> int:
         # agreed by every rank: a rank without a worker skips the collective path for all
         names = [p.strip() for p in args.enrich_local_presets.split(",") if p.strip()]
         have = sum(1 for n in names if n in pools)  # the per-rank preset workers (not rank 0's pool)
-        if args.enrich == "none" and args.enrich_local_classes > 0 and \
+        if args.full and args.enrich == "none" and args.enrich_local_classes > 0 and \
                 ctx.sum(1.0 if have == len(names) else 0.0)[0] == world:
             for name in names:
                 key = EXTRA_KEYS.get(name, "enrichLocal_" + name)

@@ -30,7 +30,7 @@ for s in $STEPS; do
     case $s in
         pytest) run pytest_gpu 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread ;;
         smoke) run smoke 600 python -c "import __graft_entry__ as g; g.smoke()" ;;
-        bench) run bench 900 python bench.py --steps 20 --warmup 5 ;;
+        bench) run bench 900 python bench.py --full --steps 20 --warmup 5 ;;
         enrich_fp8) run enrich_fp8 900 python bench_enrich.py --kv-dtype fp8 ;;
         enrich_bf16) run enrich_bf16 900 python bench_enrich.py --kv-dtype bf16 ;;
         enrich_llama) run enrich_llama 900 python bench_enrich.py --preset llama3.2-1b-code --kv-dtype fp8 ;;

@@ -22,7 +22,7 @@ def _free_port():
 
 def test_bench_single_process(capsys):
     import bench
-    assert bench.main(["--steps", "2", "--warmup", "1", "--classes", "40", "--queries", "12"]) == 0
+    assert bench.main(["--full", "--steps", "2", "--warmup", "1", "--classes", "40", "--queries", "12"]) == 0
     lines = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
     assert len(lines) == 1
     rec = json.loads(lines[0])
@@ -33,12 +33,44 @@ def test_bench_single_process(capsys):
     assert rec["extra"]["graphQueryMs"]["p50"] > 0
 
 
+def test_bench_plain_run_is_headline_only_and_dumps_its_outputs(capsys, tmp_path):
+    """Without --full: the headline alone (no secondary measurement in
+    extra), --steps timed steps, and --dump-outputs writes the last step's
+    result as float arrays that a second run with the same arguments repeats."""
+    import numpy as np
+    import bench
+    dumps = []
+    for name in ("a", "b"):
+        out = tmp_path / name
+        assert bench.main(["--steps", "3", "--warmup", "1", "--classes", "40", "--dump-outputs", str(out)]) == 0
+        lines = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
+        assert len(lines) == 1
+        rec = json.loads(lines[0])
+        assert KEYS <= set(rec) and rec["steps"] == 3 and rec["ms_per_step"] > 0
+        assert rec["metric"] == "classes indexed/sec" and rec["unit"] == "classes/s"
+        # value and ms_per_step describe the same 3 timed steps of 41 classes
+        assert rec["value"] == pytest.approx(41 * 1e3 / rec["ms_per_step"], rel=1e-3)
+        assert set(rec["extra"]) == {"phaseMsPerStep", "classesPerRepo", "parserThreadsPerRank"}
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["analysis.npy", "class_table.npy", "graph_json.npy"]
+        dumps.append({f[:-4]: np.load(out / f) for f in files})
+    a, b = dumps
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["analysis"][0] == 41 and a["analysis"][2] == 41 and a["class_table"].shape == (41, 5)
+    assert a["analysis"][1] == a["class_table"][:, 3].sum() > 0  # endpoints found = endpoint methods in the graph
+    graph = json.loads(bytes(a["graph_json"].astype(np.uint8)).decode("utf-8"))
+    assert len(graph["nodes"]) == 41 and "co.acme.shop0.order.OrderService" in graph["nodes"]
+    for f in a:
+        assert np.array_equal(a[f], b[f]), f
+
+
 @pytest.mark.timeout(600)
 def test_bench_two_ranks_gloo():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", PYTHONPATH=ROOT, CUDA_VISIBLE_DEVICES="")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
-           "--steps", "1", "--warmup", "1", "--classes", "30", "--queries", "6"]
+           "--full", "--steps", "1", "--warmup", "1", "--classes", "30", "--queries", "6"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=540)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
