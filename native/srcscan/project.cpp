@@ -21,6 +21,8 @@
 #include <algorithm>
 #include <chrono>
 #include <dirent.h>
+#include <exception>
+#include <mutex>
 #include <string>
 #include <unordered_map>
 #include <unordered_set>
@@ -106,6 +108,64 @@ void write_file(JsonWriter& w, const FileRec& f) {
     w.end_obj();
 }
 
+// Feeds ScanOptions::file_sink the completed contiguous prefix of `files`
+// while a parallel_for still parses later ones.  parallel_for hands indices
+// out from one counter, so the prefix trails the workers by about one file
+// per thread.  Whichever worker moves the prefix a chunk past the last
+// delivery makes the next one; `delivering_` keeps deliveries one at a time
+// and in order without holding the mutex across the sink call.
+class PrefixSink {
+public:
+    PrefixSink(const std::vector<FileRec>& files, const ScanOptions& opt)
+        : files_(files), sink_(opt.file_sink), chunk_(std::max<size_t>(1, opt.sink_chunk)) {
+        if (sink_) done_.assign(files.size(), 0);
+    }
+
+    void done(size_t k) {  // any worker, after files[k]'s front-end returned
+        if (!sink_) return;
+        std::unique_lock<std::mutex> lk(mu_);
+        done_[k] = 1;
+        while (prefix_ < done_.size() && done_[prefix_]) ++prefix_;
+        deliver(lk, chunk_);
+    }
+
+    void finish() {  // after the loop: every file is done
+        if (!sink_) return;
+        std::unique_lock<std::mutex> lk(mu_);
+        deliver(lk, 1);
+        if (error_) std::rethrow_exception(error_);
+    }
+
+private:
+    void deliver(std::unique_lock<std::mutex>& lk, size_t at_least) {
+        if (delivering_) return;  // that worker re-checks the prefix when it is back
+        delivering_ = true;
+        while (!error_ && prefix_ - sent_ >= at_least) {
+            const size_t first = sent_, last = prefix_;
+            sent_ = last;
+            lk.unlock();
+            std::exception_ptr err;
+            try {
+                sink_(files_, first, last);
+            } catch (...) {
+                err = std::current_exception();
+            }
+            lk.lock();
+            if (err) error_ = err;
+        }
+        delivering_ = false;
+    }
+
+    const std::vector<FileRec>& files_;
+    const std::function<void(const std::vector<FileRec>&, size_t, size_t)>& sink_;
+    const size_t chunk_;
+    std::mutex mu_;
+    std::vector<char> done_;
+    size_t prefix_ = 0, sent_ = 0;
+    bool delivering_ = false;
+    std::exception_ptr error_;
+};
+
 // ------------------------------------------------------------------- Java
 void scan_java(const std::string& root, const ScanOptions& opt, ScanResult& res) {
     std::vector<FileRec>& files = res.files;
@@ -119,16 +179,22 @@ void scan_java(const std::string& root, const ScanOptions& opt, ScanResult& res)
     res.walk_us = us_since(t);
     t = std::chrono::steady_clock::now();
     files.resize(rels.size());
-    std::vector<std::string> sources(rels.size());
+    // paths and (path-derived) identifiers of every file first: a row sink
+    // needs all identifiers to know which file of a colliding pair wins
     parallel_for(rels.size(), opt.threads, [&](size_t k) {
         FileRec& f = files[k];
         f.rel_path = src_root + "/" + rels[k];
         f.abs_path = join_path(root, f.rel_path);
         f.identifier = dotted(strip_ext(rels[k], ".java"));
-        std::string src;
-        if (!read_file(f.abs_path, src)) return;
-        analyze_java(src, f);
     });
+    PrefixSink sink(files, opt);
+    parallel_for(rels.size(), opt.threads, [&](size_t k) {
+        FileRec& f = files[k];
+        std::string src;
+        if (read_file(f.abs_path, src)) analyze_java(src, f);
+        sink.done(k);
+    });
+    sink.finish();  // the remainder, before the resolution pass touches a file
     for (auto& f : files) if (!f.parsed) ++res.skipped;
     res.analyze_us = us_since(t);
     t = std::chrono::steady_clock::now();
@@ -217,7 +283,10 @@ void scan_ts(const std::string& root, const ScanOptions& opt, std::vector<FileRe
         bool jsx = !ends_with(f.rel_path, ".ts");
         analyze_ts(src, f.rel_path, fw_name, jsx, f);
     });
-    // drop skipped files entirely (they never become graph nodes)
+    // drop skipped files entirely (they never become graph nodes).  This
+    // moves every kept FileRec (indices and string addresses change), so no
+    // row sink runs during the loop above: TypeScript rows are emitted after
+    // the scan, from the compacted vector.
     std::vector<FileRec> kept;
     kept.reserve(files.size());
     for (auto& f : files) {

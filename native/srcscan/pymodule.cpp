@@ -17,11 +17,18 @@
 #include "gitobj.hpp"
 #include "graphjson.hpp"
 #include "srcscan.hpp"
+#include "staticrows.hpp"
 #include "wire.hpp"
 
 namespace py = pybind11;
 
 namespace {
+
+using staticrows::StaticRowsEmitter;
+using staticrows::StaticRowsKeep;
+using staticrows::StaticRowsSpec;
+using staticrows::stream_rows_enabled;
+using staticrows::Uuid7Gen;
 
 // sequence (list / tuple) of equal-length tuples of None / int / float / str
 // -> one flattened batch (CPython API directly, GIL held).  Text values are
@@ -70,9 +77,13 @@ dbw::Batch to_batch(const std::string& sql, py::handle rows) {
     return b;
 }
 
-// (relative path, bytes) pairs -> scan of the mounted in-memory tree (GIL released)
-srcscan::ScanResult scan_mounted(py::list files, const std::string& language, int threads,
-                                 const std::string& framework, bool go_doc = true) {
+// (relative path, bytes) pairs -> scan of the mounted in-memory tree into
+// ``r`` (GIL released).  ``sink``: ScanOptions::file_sink; ``after_scan``
+// runs once the scan has returned, still without the GIL.
+void scan_mounted_into(py::list files, const std::string& language, int threads, const std::string& framework,
+                       bool go_doc, srcscan::ScanResult& r,
+                       std::function<void(const std::vector<srcscan::FileRec>&, size_t, size_t)> sink = nullptr,
+                       const std::function<void()>& after_scan = nullptr) {
     const auto t = std::chrono::steady_clock::now();
     // contents are viewed in place: the (path, bytes) tuples are held
     // (immutable bytes) until the scan is done
@@ -100,15 +111,23 @@ srcscan::ScanResult scan_mounted(py::list files, const std::string& language, in
     opt.threads = threads;
     opt.framework = framework;
     opt.go_doc = go_doc;
+    opt.file_sink = std::move(sink);
     try {
-        srcscan::ScanResult r = srcscan::scan_project(root, opt);
+        srcscan::scan_project_into(root, opt, r);
         r.mount_us = mount_us;
-        srcscan::vfs_unmount(root);
-        return r;
+        if (after_scan) after_scan();
     } catch (...) {
         srcscan::vfs_unmount(root);
         throw;
     }
+    srcscan::vfs_unmount(root);
+}
+
+srcscan::ScanResult scan_mounted(py::list files, const std::string& language, int threads,
+                                 const std::string& framework, bool go_doc = true) {
+    srcscan::ScanResult r;
+    scan_mounted_into(files, language, threads, framework, go_doc, r);
+    return r;
 }
 
 py::str pystr(const std::string& s) {
@@ -164,30 +183,15 @@ void json_str_list_ascii(PyObject* seq, std::string& out) {
     out.push_back(']');
 }
 
-struct RowBuilder {
-    dbw::Batch b;
-    explicit RowBuilder(const std::string& sql, int ncols) {
-        b.sql = sql;
-        b.ncols = ncols;
-    }
-    void null() { b.values.emplace_back(); }
-    void text(const char* p, Py_ssize_t n) {
-        dbw::Value v;
-        v.kind = dbw::Value::Text;
-        v.p = p;
-        v.n = static_cast<int32_t>(n);
-        b.values.push_back(v);
-    }
+// staticrows::TextRows plus values taken from Python objects (GIL held)
+struct RowBuilder : staticrows::TextRows {
+    using staticrows::TextRows::TextRows;
     void str(PyObject* o) {  // a str the caller keeps alive, or None
         if (o == Py_None) return null();
         Py_ssize_t n = 0;
         const char* p = PyUnicode_AsUTF8AndSize(o, &n);
         if (!p) throw py::error_already_set();
-        text(p, n);
-    }
-    void owned(std::string&& s) {
-        b.owned.push_back(std::move(s));
-        text(b.owned.back().data(), (Py_ssize_t)b.owned.back().size());
+        text(p, static_cast<size_t>(n));
     }
     void integer_or_null(PyObject* o) {
         if (o == Py_None) return null();
@@ -197,13 +201,6 @@ struct RowBuilder {
         if (v.i == -1 && PyErr_Occurred()) throw py::error_already_set();
         b.values.push_back(v);
     }
-    void integer(long long i) {
-        dbw::Value v;
-        v.kind = dbw::Value::Int;
-        v.i = i;
-        b.values.push_back(v);
-    }
-    bool empty() const { return b.values.empty(); }
 };
 
 PyObject* getattr_borrowed(PyObject* o, const char* name, std::vector<py::object>& hold) {
@@ -355,190 +352,6 @@ py::dict scan_result_objects(const srcscan::ScanResult& r, py::handle method_cls
 // class, its methods, ..., then parameter links) and the same values.
 // The caller keeps ``order``, ``units``, ``ids`` and the scalar strings alive
 // until the writer has finished (text values are views into them).
-// Time-ordered version-7 UUID strings (RFC 9562): 48-bit ms timestamp, then
-// a 74-bit counter started at a random point (rand_a + rand_b), so a batch is
-// strictly increasing and bulk inserts append to the primary-key B-trees.
-struct Uuid7Gen {
-    unsigned long long ms = 0, hi = 0, lo = 0;
-    Uuid7Gen() {
-        unsigned char seed[10];
-        if (getrandom(seed, sizeof(seed), 0) != (ssize_t)sizeof(seed)) throw std::runtime_error("getrandom failed");
-        ms = (unsigned long long)std::chrono::duration_cast<std::chrono::milliseconds>(
-                 std::chrono::system_clock::now().time_since_epoch())
-                 .count();
-        // counter: 12 bits (rand_a) + 62 bits (rand_b); start in the lower half to avoid overflow
-        hi = ((unsigned long long)(seed[0] & 0x07) << 8) | seed[1];  // 11 bits
-        for (int j = 2; j < 10; ++j) lo = (lo << 8) | seed[j];
-        lo &= 0x1FFFFFFFFFFFFFFFull;  // 61 bits
-    }
-    void next(char* s) {  // 36 chars
-        static const char* hex = "0123456789abcdef";
-        unsigned char b[16];
-        for (int j = 0; j < 6; ++j) b[j] = (unsigned char)(ms >> (8 * (5 - j)));
-        b[6] = (unsigned char)(0x70 | ((hi >> 8) & 0x0F));
-        b[7] = (unsigned char)(hi & 0xFF);
-        b[8] = (unsigned char)(0x80 | ((lo >> 56) & 0x3F));
-        for (int j = 9; j < 16; ++j) b[j] = (unsigned char)(lo >> (8 * (15 - j)));
-        if (++lo >> 62) {
-            lo = 0;
-            ++hi;
-        }
-        int k = 0;
-        for (int j = 0; j < 16; ++j) {
-            if (j == 4 || j == 6 || j == 8 || j == 10) s[k++] = '-';
-            s[k++] = hex[b[j] >> 4];
-            s[k++] = hex[b[j] & 15];
-        }
-    }
-};
-
-// json.dumps(list_of_str) (default separators, ensure_ascii) of UTF-8 strings
-void json_ascii_list(const std::vector<std::string>& v, std::string& out) {
-    static const char* hex = "0123456789abcdef";
-    auto u4 = [&](unsigned c) {
-        out += "\\u";
-        for (int sh = 12; sh >= 0; sh -= 4) out += hex[(c >> sh) & 15];
-    };
-    out = "[";
-    for (size_t i = 0; i < v.size(); ++i) {
-        if (i) out += ", ";
-        out += '"';
-        const std::string& s = v[i];
-        for (size_t k = 0; k < s.size();) {
-            unsigned char c = (unsigned char)s[k];
-            unsigned cp = c;
-            size_t len = 1;
-            if (c >= 0xF0 && k + 3 < s.size() + 0) { cp = ((c & 7u) << 18) | ((s[k + 1] & 63u) << 12) | ((s[k + 2] & 63u) << 6) | (s[k + 3] & 63u); len = 4; }
-            else if (c >= 0xE0 && k + 2 < s.size()) { cp = ((c & 15u) << 12) | ((s[k + 1] & 63u) << 6) | (s[k + 2] & 63u); len = 3; }
-            else if (c >= 0xC0 && k + 1 < s.size()) { cp = ((c & 31u) << 6) | (s[k + 1] & 63u); len = 2; }
-            k += len;
-            if (cp == '"') out += "\\\"";
-            else if (cp == '\\') out += "\\\\";
-            else if (cp == '\n') out += "\\n";
-            else if (cp == '\r') out += "\\r";
-            else if (cp == '\t') out += "\\t";
-            else if (cp == '\b') out += "\\b";
-            else if (cp == '\f') out += "\\f";
-            else if (cp < 0x20 || (cp >= 0x7f && cp < 0x10000)) u4(cp);
-            else if (cp >= 0x10000) {
-                cp -= 0x10000;
-                u4(0xD800 + (cp >> 10));
-                u4(0xDC00 + (cp & 0x3FF));
-            } else out += (char)cp;
-        }
-        out += '"';
-    }
-    out += "]";
-}
-
-// Class and method rows of a finished scan handed to the bulk writer at once
-// (before any Python object exists), so the inserts start while the caller
-// still builds the graph; Phase 1 then only binds the ids (phase1_rows with
-// pre_ids) and writes the parameter rows.  Java / TypeScript units (a later
-// file with the same identifier replaces the earlier one, as
-// parsers/base.py::_add_unit does); Go merges files per package: not here.
-// The rows view the ScanResult's strings and one id buffer, which the
-// batches keep alive (freed on the writer thread after the inserts).
-struct StaticRowsSpec {
-    dbw::BulkWriter* writer = nullptr;
-    std::string pid, now, commit, cls_sql, meth_sql;
-    bool commit_null = false;
-};
-
-struct StaticRowsKeep {
-    std::shared_ptr<const srcscan::ScanResult> r;
-    StaticRowsSpec spec;
-    std::string ids;                  // 36 chars per id: per emitted file its class id, then its method ids
-    std::vector<size_t> first;        // per file: offset of its class id in `ids` (npos: replaced file)
-    std::deque<std::string> strings;  // JSON exception lists
-};
-
-const std::string& normalize_class_type(const std::string& t) {
-    static const std::string kTypes[] = {"CONTROLLER", "SERVICE", "REPOSITORY", "ENTITY", "DTO",
-                                         "CONFIGURATION", "LISTENER", "UTILITY", "EXCEPTION", "OTHER"};
-    for (const std::string& k : kTypes) {
-        if (k.size() != t.size()) continue;
-        bool eq = true;
-        for (size_t i = 0; i < t.size() && eq; ++i) eq = std::toupper((unsigned char)t[i]) == k[i];
-        if (eq) return k;
-    }
-    return kTypes[9];  // ClassType.from_string: OTHER
-}
-
-// GIL not needed: reads the (const) ScanResult, which a concurrent Python
-// object build may read too
-void emit_static_rows(const std::shared_ptr<StaticRowsKeep>& keep) {
-    const srcscan::ScanResult& r = *keep->r;
-    const StaticRowsSpec& spec = keep->spec;
-    std::unordered_map<std::string_view, size_t> last;
-    last.reserve(r.files.size() * 2);
-    size_t n_ids = 0;
-    for (size_t k = 0; k < r.files.size(); ++k) last[r.files[k].identifier] = k;
-    for (size_t k = 0; k < r.files.size(); ++k)
-        if (last[r.files[k].identifier] == k) n_ids += 1 + r.files[k].methods.size();
-    keep->ids.resize(36 * n_ids);  // never reallocated below: rows view it
-    keep->first.assign(r.files.size(), std::string::npos);
-    Uuid7Gen gen;
-    size_t at = 0;
-    const int chunk = 256;
-    RowBuilder cls(spec.cls_sql, 10), meth(spec.meth_sql, 10);
-    int pending = 0;
-    auto flush = [&]() {
-        cls.b.keep = keep;
-        meth.b.keep = keep;
-        if (!cls.empty()) spec.writer->put(std::move(cls.b));
-        if (!meth.empty()) spec.writer->put(std::move(meth.b));
-        cls = RowBuilder(spec.cls_sql, 10);
-        meth = RowBuilder(spec.meth_sql, 10);
-        pending = 0;
-    };
-    auto sv = [](RowBuilder& b, const std::string& s) { b.text(s.data(), (Py_ssize_t)s.size()); };
-    for (size_t k = 0; k < r.files.size(); ++k) {
-        const srcscan::FileRec& f = r.files[k];
-        if (last[f.identifier] != k) continue;
-        if (pending == chunk) flush();
-        ++pending;
-        keep->first[k] = at;
-        const char* cid = &keep->ids[at];
-        gen.next(&keep->ids[at]);
-        at += 36;
-        const std::string& ident = f.identifier;
-        const size_t dot = ident.rfind('.');
-        cls.text(cid, 36);
-        sv(cls, spec.pid);
-        sv(cls, ident);
-        if (dot != std::string::npos) cls.text(ident.data() + dot + 1, (Py_ssize_t)(ident.size() - dot - 1));
-        else sv(cls, ident);
-        if (dot != std::string::npos) cls.text(ident.data(), (Py_ssize_t)dot); else cls.null();
-        sv(cls, normalize_class_type(f.class_type));
-        cls.null();
-        sv(cls, f.rel_path);
-        sv(cls, spec.now);
-        if (spec.commit_null) cls.null(); else sv(cls, spec.commit);
-        for (const srcscan::MethodRec& m : f.methods) {
-            gen.next(&keep->ids[at]);
-            meth.text(&keep->ids[at], 36);
-            at += 36;
-            meth.text(cid, 36);
-            sv(meth, m.name);
-            meth.null();
-            meth.text("[]", 2);
-            if (m.exceptions.empty()) {
-                meth.text("[]", 2);
-            } else {
-                keep->strings.emplace_back();
-                json_ascii_list(m.exceptions, keep->strings.back());
-                sv(meth, keep->strings.back());
-            }
-            if (m.has_http_method) sv(meth, m.http_method); else meth.null();
-            if (m.has_http_path) sv(meth, m.http_path); else meth.null();
-            meth.integer(m.line);
-            sv(meth, spec.now);
-        }
-    }
-    flush();
-}
-
 py::tuple phase1_rows(dbw::BulkWriter& writer, py::list order, py::dict units, py::object ids, py::str pid,
                       py::str now, py::handle commit_hash, const std::string& cls_sql, const std::string& meth_sql,
                       const std::string& param_sql, py::handle method_info_cls, int chunk, py::object graph_targets,
@@ -837,33 +650,51 @@ py::tuple phase1_rows(dbw::BulkWriter& writer, py::list order, py::dict units, p
 
 }  // namespace
 
-// The Python objects of a scan (scan_result_objects) and, with rows =
-// (BulkWriter, project id, now, commit hash | None, class INSERT, method
-// INSERT), its class / method rows streamed to the writer from a helper thread
-// while this one builds the objects (row ids in d["rowIds"]).  Shared by the
-// in-process scan and the isolated child's binary result.
-py::dict objects_and_rows(std::shared_ptr<const srcscan::ScanResult> shared, py::handle method_cls, py::object rows) {
-    std::shared_ptr<StaticRowsKeep> keep;
+// rows = (BulkWriter, project id, now, commit hash | None, class INSERT,
+// method INSERT) | None -> the emitter of ``shared``'s rows (null for None).
+// ``shared`` is owned before the scan fills it: the batches' keep pointer
+// holds it, and its files' addresses never move once they are sized.
+std::unique_ptr<StaticRowsEmitter> rows_emitter(py::object rows, std::shared_ptr<const srcscan::ScanResult> shared) {
+    if (rows.is_none()) return nullptr;
+    py::tuple rt = rows.cast<py::tuple>();
+    if (rt.size() != 6) throw py::value_error("rows must have 6 items");
+    auto keep = std::make_shared<StaticRowsKeep>();
+    keep->r = std::move(shared);
+    StaticRowsSpec& spec = keep->spec;
+    spec.writer = &rt[0].cast<dbw::BulkWriter&>();
+    spec.pid = rt[1].cast<std::string>();
+    spec.now = rt[2].cast<std::string>();
+    spec.commit_null = rt[3].is_none();
+    if (!spec.commit_null) spec.commit = rt[3].cast<std::string>();
+    spec.cls_sql = rt[4].cast<std::string>();
+    spec.meth_sql = rt[5].cast<std::string>();
+    return std::make_unique<StaticRowsEmitter>(std::move(keep));
+}
+
+// The Python objects of a scan (scan_result_objects) and, with an emitter
+// (rows_emitter), its class / method rows in the writer and their ids in
+// d["rowIds"].  Two emissions end here:
+//  * streamed (Java in process, DMCP_STREAM_ROWS on): the scan's row sink
+//    queued finished file ranges for the emitter's own thread while later
+//    files were still parsed, so the inserts started under the parse; ``em``
+//    arrives finished and only the ids are read out;
+//  * after the scan (TypeScript, whose scan compacts its file vector after
+//    the parse; the isolated child's decoded result; DMCP_STREAM_ROWS=0): a
+//    helper thread emits all rows while this one builds the objects.
+// Either way the writer sees the rows in file order with ascending ids.
+py::dict objects_and_rows(std::shared_ptr<const srcscan::ScanResult> shared, py::handle method_cls,
+                          std::unique_ptr<StaticRowsEmitter> em) {
+    if (em && shared->language == "go") em.reset();  // Go merges files per package: Phase 1 writes its rows
     std::thread emitter;
-    std::atomic<long long> emit_us{0};
-    if (!rows.is_none() && shared->language != "go") {
-        py::tuple rt = rows.cast<py::tuple>();
-        if (rt.size() != 6) throw py::value_error("rows must have 6 items");
-        keep = std::make_shared<StaticRowsKeep>();
-        keep->r = shared;
-        StaticRowsSpec& spec = keep->spec;
-        spec.writer = &rt[0].cast<dbw::BulkWriter&>();
-        spec.pid = rt[1].cast<std::string>();
-        spec.now = rt[2].cast<std::string>();
-        spec.commit_null = rt[3].is_none();
-        if (!spec.commit_null) spec.commit = rt[3].cast<std::string>();
-        spec.cls_sql = rt[4].cast<std::string>();
-        spec.meth_sql = rt[5].cast<std::string>();
-        emitter = std::thread([keep, &emit_us] {
-            const auto t = std::chrono::steady_clock::now();
-            emit_static_rows(keep);
-            emit_us = std::chrono::duration_cast<std::chrono::microseconds>(
-                          std::chrono::steady_clock::now() - t).count();
+    std::exception_ptr emit_error;
+    if (em && !em->finished()) {
+        emitter = std::thread([&em, &shared, &emit_error] {
+            try {
+                em->feed(shared->files, em->fed(), shared->files.size());
+                em->finish();
+            } catch (...) {
+                emit_error = std::current_exception();
+            }
         });
     }
     py::dict d;
@@ -880,26 +711,30 @@ py::dict objects_and_rows(std::shared_ptr<const srcscan::ScanResult> shared, py:
         }
         throw;
     }
-    if (emitter.joinable()) {
-        {
+    if (em) {
+        if (emitter.joinable()) {
             py::gil_scoped_release release;
             emitter.join();
         }
-        py::dict(d["stats"])["phaseUs"].cast<py::dict>()["rows"] = emit_us.load();
+        if (emit_error) std::rethrow_exception(emit_error);
+        const StaticRowsKeep& keep = *em->keep();
+        py::dict stats(d["stats"]);
+        stats["phaseUs"].cast<py::dict>()["rows"] = em->us();
+        stats["streamedFiles"] = em->streamed;  // 0: all rows were emitted after the scan
         py::dict row_ids;
-        for (size_t k = 0; k < shared->files.size(); ++k) {
-            const size_t at = keep->first[k];
-            if (at == std::string::npos) continue;  // a file replaced by a later one
+        for (size_t k = 0; k < keep.first.size(); ++k) {
+            const char* at = keep.first[k];
+            if (at == nullptr) continue;  // a file replaced by a later one
             const size_t nm = shared->files[k].methods.size();
             py::list mids(nm);
-            for (size_t j = 0; j < nm; ++j) mids[j] = py::str(&keep->ids[at + 36 * (j + 1)], 36);
-            row_ids[pystr(shared->files[k].identifier)] = py::make_tuple(py::str(&keep->ids[at], 36), mids);
+            for (size_t j = 0; j < nm; ++j) mids[j] = py::str(at + 36 * (j + 1), 36);
+            row_ids[pystr(shared->files[k].identifier)] = py::make_tuple(py::str(at, 36), mids);
         }
         d["rowIds"] = row_ids;
     }
     // the rest of the ScanResult is freed off this thread (by the
     // writer after its inserts, or here by a helper)
-    keep.reset();
+    em.reset();
     std::thread([](std::shared_ptr<const srcscan::ScanResult>) {}, std::move(shared)).detach();
     return d;
 }
@@ -955,9 +790,24 @@ PYBIND11_MODULE(_srcscan, m) {
         "scan_sources_objects",
         [](py::list files, const std::string& language, int threads, const std::string& framework,
            py::handle method_cls, py::object rows, bool go_doc) {
-            auto r = std::make_unique<srcscan::ScanResult>(scan_mounted(files, language, threads, framework,
-                                                                        go_doc));
-            return objects_and_rows(std::shared_ptr<const srcscan::ScanResult>(std::move(r)), method_cls, rows);
+            // the result is owned (and shared with the rows' batches) before
+            // the scan starts: rows may reach the writer while it runs
+            auto r = std::make_shared<srcscan::ScanResult>();
+            std::unique_ptr<StaticRowsEmitter> em = rows_emitter(rows, r);
+            if (em && stream_rows_enabled()) {
+                // the sink (scan worker threads, no GIL) queues ranges for the
+                // emitter's thread; neither touches a Python object.  A scan
+                // that throws stops the thread on the way out: the rows queued
+                // so far stay in the writer for the caller's abort
+                staticrows::EmitterThread feeder(*em);
+                scan_mounted_into(
+                    files, language, threads, framework, go_doc, *r,
+                    [&feeder](const std::vector<srcscan::FileRec>&, size_t a, size_t b) { feeder.push(a, b); },
+                    [&feeder] { feeder.close(); });
+            } else {
+                scan_mounted_into(files, language, threads, framework, go_doc, *r);
+            }
+            return objects_and_rows(std::move(r), method_cls, std::move(em));
         },
         py::arg("files"), py::arg("language"), py::arg("threads"), py::arg("framework"), py::arg("method_cls"),
         py::arg("rows") = py::none(), py::arg("go_doc") = true,
@@ -980,7 +830,8 @@ PYBIND11_MODULE(_srcscan, m) {
                 ok = srcscan::decode_result(std::string_view(data, static_cast<size_t>(n)), *r, err);
             }
             if (!ok) throw py::value_error("scan result: " + err);
-            return objects_and_rows(std::shared_ptr<const srcscan::ScanResult>(std::move(r)), method_cls, rows);
+            std::shared_ptr<const srcscan::ScanResult> shared(std::move(r));
+            return objects_and_rows(shared, method_cls, rows_emitter(rows, shared));
         },
         py::arg("blob"), py::arg("method_cls"), py::arg("rows") = py::none(),
         "the binary ScanResult of `srcscan serve` as scan_sources_objects returns it (untrusted bytes: every "
@@ -1216,5 +1067,6 @@ PYBIND11_MODULE(_srcscan, m) {
             d["t_end_s"] = w.t_end();
             return d;
         });
-    m.attr("ABI_VERSION") = 6;  // 6: scan_sources_objects(..., go_doc=)
+    // 6: scan_sources_objects(..., go_doc=); 7: Java rows streamed during the scan (DMCP_STREAM_ROWS)
+    m.attr("ABI_VERSION") = 7;
 }

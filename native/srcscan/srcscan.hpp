@@ -1,6 +1,7 @@
 // srcscan public data model and entry points.
 #pragma once
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -31,6 +32,11 @@ struct ImportRec {
 };
 
 // Per-file front-end result.
+// The resolution pass writes only `deps` and `params`; everything else is
+// final once the file's front-end has returned.  Rows streamed to the
+// database writer during a scan (ScanOptions::file_sink) view `identifier`,
+// `rel_path`, `class_type` and the methods' `name`, `exceptions`,
+// `http_method`, `http_path` and `line` -- never the two resolved fields.
 struct FileRec {
     std::string abs_path;
     std::string rel_path;      // relative to the project root, '/' separated
@@ -74,6 +80,16 @@ struct ScanOptions {
     std::string framework;          // TS only: override detection
     size_t max_file_bytes = 5u * 1024u * 1024u;  // NodeJsGraalParser.java:57
     bool go_doc = true;             // Go only: also render the go-analyzer package document
+    // Optional row sink (Java only): called with finished ranges [first, last)
+    // of ScanResult::files while later files are still being parsed.  Every
+    // file's rel_path and identifier are set before the first call; files in
+    // a delivered range also have their front-end fields final (see FileRec).
+    // Ranges arrive in increasing order, cover every file exactly once before
+    // the resolution pass starts, and are never delivered concurrently -- but
+    // on whichever scan worker thread completed the range.  A sink that
+    // throws stops the deliveries; the scan rethrows after its per-file loop.
+    std::function<void(const std::vector<FileRec>& files, size_t first, size_t last)> file_sink;
+    size_t sink_chunk = 64;         // files per delivery (the last one may be shorter)
 };
 
 // Result of a project scan (what the JSON document of project.cpp holds).
