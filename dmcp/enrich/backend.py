@@ -460,6 +460,18 @@ def create_backend(cfg) -> EnrichmentBackend:
                       f"LOCAL_LLM_ALLOW_RANDOM_WEIGHTS=true for benchmarks and tests")
             LOG.error("%s", reason)
             return RefusedBackend(reason)
+        path = (getattr(cfg, "local_llm_model_path", "") or "").strip()
+        if path and os.path.isfile(os.path.join(path, "config.json")):
+            # a checkpoint the loader cannot reproduce (config.json + safetensors
+            # headers only: no worker process, no tensor data) is refused here,
+            # not loaded as some other model
+            from ..models.llm import check_checkpoint
+            why = check_checkpoint(path)
+            if why is not None:
+                reason = (f"ENRICH_BACKEND=local cannot load the checkpoint LOCAL_LLM_MODEL_PATH={path}: {why}. "
+                          f"Supported: Llama and Qwen2 checkpoints (docs/PARITY.md)")
+                LOG.error("%s", reason)
+                return RefusedBackend(reason)
 
         def build() -> EnrichmentBackend:
             from .local import LocalLLMBackend

@@ -40,7 +40,9 @@ MI355X mapping:
   (:class:`DecodeGraphs`), removing ~10 launches/layer of host overhead.
 
 Weights are random-initialised by default (no checkpoint on this host) or
-loaded from a Llama-format safetensors directory (``load_safetensors``).
+loaded from a Llama- or Qwen2-format safetensors directory
+(``load_safetensors``: RoPE scaling and q/k/v biases included; a directory
+it cannot reproduce is refused, ``check_checkpoint``).
 """
 from __future__ import annotations
 
@@ -94,6 +96,10 @@ class LMConfig:
     # the preset's tokenizer: "" = byte-level (dmcp.enrich.tokenizer.ByteTokenizer),
     # else an asset directory under dmcp/models/assets (tokenizer.json.gz)
     tokenizer: str = ""
+    # RoPE frequency scaling of a loaded checkpoint: None, or the sorted
+    # (key, value) pairs of its rope_scaling dict (ops.reference.rope_scaling_key:
+    # "linear" or "llama3"; hashable, so a config stays a dict key)
+    rope_scaling: Optional[tuple] = None
 
     @property
     def qkv_dim(self) -> int:
@@ -180,6 +186,112 @@ MXFP8_CHECKPOINT_GATE = {"cosine": 0.995, "top1": 0.75}
 MXFP8_CHECKPOINT_OK = False
 
 
+class CheckpointUnsupported(ValueError):
+    """A checkpoint directory this loader cannot reproduce faithfully
+    (:func:`check_checkpoint` gives the reason)."""
+
+
+SUPPORTED_MODEL_TYPES = ("llama", "qwen2")
+SUPPORTED_ARCHITECTURES = ("LlamaForCausalLM", "Qwen2ForCausalLM")
+_LAYER_TENSORS = ("input_layernorm.weight", "post_attention_layernorm.weight", "self_attn.q_proj.weight",
+                  "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.o_proj.weight",
+                  "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
+_QKV_BIASES = ("self_attn.q_proj.bias", "self_attn.k_proj.bias", "self_attn.v_proj.bias")
+
+
+def _checkpoint_rope(hf: dict) -> Tuple[float, Optional[tuple]]:
+    """(theta, LMConfig.rope_scaling) of a config.json: ``rope_scaling`` keyed
+    by ``rope_type`` or the legacy ``type``, or the newer ``rope_parameters``
+    dict, which may carry ``rope_theta`` too.  ValueError on an unsupported type."""
+    params = hf.get("rope_parameters") or {}
+    scaling = hf.get("rope_scaling") or params
+    theta = hf.get("rope_theta", params.get("rope_theta", 10000.0))
+    return float(theta), ops.reference.rope_scaling_key(scaling)
+
+
+def _checkpoint_tensor_names(path: str) -> List[str]:
+    """Tensor names of every *.safetensors file of a directory (headers only)."""
+    from safetensors import safe_open
+    names: List[str] = []
+    for fn in sorted(os.listdir(path)):
+        if fn.endswith(".safetensors"):
+            with safe_open(os.path.join(path, fn), framework="pt") as f:
+                names.extend(f.keys())
+    return names
+
+
+def check_checkpoint(path: str) -> Optional[str]:
+    """Why the checkpoint directory ``path`` cannot be loaded as the model it
+    is -- naming the config key or tensor -- or None when
+    :meth:`LocalLM.load_safetensors` reproduces it.  Reads ``config.json`` and
+    the safetensors headers only: no tensor data, no device."""
+    cfg_path = os.path.join(path, "config.json")
+    try:
+        with open(cfg_path) as f:
+            hf = json.load(f)
+    except (OSError, ValueError) as e:
+        return f"config.json of {path} cannot be read ({e})"
+    mt = hf.get("model_type")
+    archs = hf.get("architectures") or []
+    if mt is not None and mt not in SUPPORTED_MODEL_TYPES:
+        return f"model_type {mt!r} is not supported (supported: {', '.join(SUPPORTED_MODEL_TYPES)})"
+    # a config naming neither is taken as the Llama layout (the tensor names below still have to match)
+    if any(a not in SUPPORTED_ARCHITECTURES for a in archs):
+        return f"architectures {archs!r} is not supported (supported: {', '.join(SUPPORTED_ARCHITECTURES)})"
+    for k in ("vocab_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size"):
+        if not isinstance(hf.get(k), int) or hf[k] <= 0:
+            return f"config.json: {k} is missing or not a positive integer"
+    act = hf.get("hidden_act", "silu")
+    if act != "silu":
+        return f"hidden_act {act!r} is not supported (the MLP kernels compute SwiGLU with silu)"
+    if hf.get("mlp_bias"):
+        return "mlp_bias true is not supported (the MLP projections take no bias)"
+    if hf.get("use_sliding_window"):
+        return "use_sliding_window true is not supported (the attention kernels attend to every cached key)"
+    heads = hf["num_attention_heads"]
+    kvh = hf.get("num_key_value_heads", heads)
+    if not isinstance(kvh, int) or kvh <= 0 or heads % kvh:
+        return f"num_attention_heads {heads} is not a multiple of num_key_value_heads {kvh}"
+    try:
+        _checkpoint_rope(hf)
+    except (ValueError, TypeError) as e:
+        return f"rope_scaling: {e}"
+    try:
+        names = _checkpoint_tensor_names(path)
+    except Exception as e:  # noqa: BLE001 -- a truncated or foreign file: refuse with its error
+        return f"safetensors of {path} cannot be read ({e})"
+    if not names:
+        return f"{path} holds no *.safetensors file"
+    layers = hf["num_hidden_layers"]
+    consumed = {"model.embed_tokens.weight", "model.norm.weight", "lm_head.weight"}
+    required = {"model.embed_tokens.weight", "model.norm.weight"}
+    for i in range(layers):
+        p = f"model.layers.{i}."
+        required.update(p + n for n in _LAYER_TENSORS)
+        consumed.update(p + n for n in _QKV_BIASES)
+    consumed |= required
+    have = set(names)
+    for n in names:  # the first tensor the loader would drop
+        if n in consumed or n.endswith("rotary_emb.inv_freq"):
+            continue
+        if n.endswith((".o_proj.bias", ".gate_proj.bias", ".up_proj.bias", ".down_proj.bias")):
+            return f"tensor {n} is not supported (only the q/k/v projections take a bias)"
+        return f"tensor {n} is not consumed by the loader (a layout other than Llama / Qwen2)"
+    missing = sorted(required - have)
+    if missing:
+        return f"tensor {missing[0]} is missing"
+    for i in range(layers):
+        p = f"model.layers.{i}."
+        nb = sum((p + n) in have for n in _QKV_BIASES)
+        if nb not in (0, 3):
+            return f"layer {i} has {nb} of the 3 q/k/v bias tensors ({p}self_attn.*_proj.bias)"
+        if hf.get("attention_bias") is False and nb:
+            return f"attention_bias is false but {p}self_attn.q_proj.bias exists"
+    if "lm_head.weight" not in have and hf.get("tie_word_embeddings") is False:
+        return "tensor lm_head.weight is missing and tie_word_embeddings is false"
+    return None
+
+
 def preset(name: str, **overrides) -> LMConfig:
     if name not in PRESETS:
         raise ValueError(f"unknown model preset {name!r}; choose one of {sorted(PRESETS)}")
@@ -261,6 +373,13 @@ class LocalLM:
         # None = random-initialised weights of a preset
         self.checkpoint: Optional[str] = None
         self.w = weights if weights is not None else self._init_weights(seed)
+        # q/k/v projection biases (Qwen2 checkpoints): w["l{i}.bqkv"], bf16 [qkv_dim]
+        self.has_bias = any(k.endswith(".bqkv") for k in self.w)
+        if self.has_bias and "fp8" in (cfg.prefill_dtype, cfg.decode_dtype):
+            raise ValueError(f"{cfg.name} has q/k/v projection biases, which the MXFP8 GEMMs do not apply: "
+                             f"use prefill_dtype / decode_dtype 'bf16' (LOCAL_LLM_PREFILL_DTYPE, "
+                             f"LOCAL_LLM_DECODE_DTYPE), got prefill_dtype={cfg.prefill_dtype!r} "
+                             f"decode_dtype={cfg.decode_dtype!r}")
         self._fold_norms()
         c = cfg
         self.shared_prefix = shared_prefix
@@ -273,7 +392,8 @@ class LocalLM:
         self._check_kv_fits(kv_shape)
         self.k_cache = torch.zeros(kv_shape, dtype=self.kv_dtype, device=self.device)
         self.v_cache = torch.zeros(kv_shape, dtype=self.kv_dtype, device=self.device)
-        self.cos_sin = ops.rope_tables(c.max_seq, c.head_dim, c.rope_theta, device=self.device).contiguous()
+        self.cos_sin = ops.rope_tables(c.max_seq, c.head_dim, c.rope_theta, device=self.device,
+                                       scaling=c.rope_scaling).contiguous()
         self.scale = 1.0 / math.sqrt(c.head_dim)
         self.max_rows = max(c.max_batch, c.max_rows)
         # method branches: per slot (parent slot, end) -- the decode attention
@@ -342,7 +462,8 @@ class LocalLM:
              and ops.pgemm_supported(c.hidden, c.n_heads, c.n_kv_heads, c.head_dim, c.intermediate))
             or (self.device.type == "cpu" and c.hidden % 32 == 0 and c.intermediate % 32 == 0))
         self.prefill_fp8 = fp8_ok and (c.prefill_dtype == "fp8"
-                                       or (c.prefill_dtype == "auto" and self.device.type == "cuda"))
+                                       or (c.prefill_dtype == "auto" and self.device.type == "cuda"
+                                           and not self.has_bias))
         self.decode_fp8 = c.decode_dtype == "fp8" and fp8_ok
         if "fp8" in (c.prefill_dtype, c.decode_dtype) and not fp8_ok:
             raise ValueError(f"fp8 GEMMs need head_dim 64, hidden % 2048 == 0 and a supported device "
@@ -454,17 +575,25 @@ class LocalLM:
 
     @classmethod
     def load_safetensors(cls, path: str, device: str = "cuda", **cfg_overrides) -> "LocalLM":
-        """Loads a Llama-format checkpoint directory (config.json + *.safetensors)."""
+        """Loads a Llama- or Qwen2-format checkpoint directory (config.json +
+        *.safetensors) as the model it is: RoPE scaling ("linear", "llama3")
+        and q/k/v projection biases included.  A directory the loader cannot
+        reproduce raises :class:`CheckpointUnsupported` with the reason
+        (:func:`check_checkpoint`)."""
         from safetensors.torch import load_file
+        reason = check_checkpoint(path)
+        if reason is not None:
+            raise CheckpointUnsupported(f"{path}: {reason}")
         with open(os.path.join(path, "config.json")) as f:
             hf = json.load(f)
         heads = hf["num_attention_heads"]
+        theta, scaling = _checkpoint_rope(hf)
         cfg = LMConfig(name=os.path.basename(path.rstrip("/")), vocab_size=hf["vocab_size"],
                        hidden=hf["hidden_size"], layers=hf["num_hidden_layers"], n_heads=heads,
                        n_kv_heads=hf.get("num_key_value_heads", heads),
-                       head_dim=hf.get("head_dim", hf["hidden_size"] // heads),
-                       intermediate=hf["intermediate_size"], rope_theta=hf.get("rope_theta", 10000.0),
-                       eps=hf.get("rms_norm_eps", 1e-5))
+                       head_dim=hf.get("head_dim") or hf["hidden_size"] // heads,
+                       intermediate=hf["intermediate_size"], rope_theta=theta,
+                       eps=hf.get("rms_norm_eps", 1e-5), rope_scaling=scaling)
         cfg = replace(cfg, **cfg_overrides)
         if cfg.prefill_dtype == "auto" and not MXFP8_CHECKPOINT_OK:
             # a real checkpoint keeps bf16 prefill GEMMs unless fp8 is asked
@@ -488,6 +617,9 @@ class LocalLM:
             w[f"l{i}.ln2"] = g(p + "post_attention_layernorm.weight")
             w[f"l{i}.wqkv"] = torch.cat([g(p + "self_attn.q_proj.weight"), g(p + "self_attn.k_proj.weight"),
                                          g(p + "self_attn.v_proj.weight")], 0).contiguous()
+            if p + "self_attn.q_proj.bias" in raw:  # Qwen2: q/k/v biases, stacked like wqkv
+                w[f"l{i}.bqkv"] = torch.cat([g(p + "self_attn.q_proj.bias"), g(p + "self_attn.k_proj.bias"),
+                                             g(p + "self_attn.v_proj.bias")], 0).contiguous()
             w[f"l{i}.wo"] = g(p + "self_attn.o_proj.weight")
             w[f"l{i}.wgu"] = torch.cat([g(p + "mlp.gate_proj.weight"), g(p + "mlp.up_proj.weight")], 0).contiguous()
             w[f"l{i}.wdown"] = g(p + "mlp.down_proj.weight")
@@ -526,7 +658,7 @@ class LocalLM:
         L = start_pos + T
         for i in range(c.layers):
             kc, vc = self.k_cache[i], self.v_cache[i]
-            qkv = F.linear(h, self.w[f"l{i}.wqkv"])
+            qkv = F.linear(h, self.w[f"l{i}.wqkv"], self.w.get(f"l{i}.bqkv"))
             q = ops.rope_kv(qkv, pos, slots, self.cos_sin, kc, vc, c.n_heads)  # [T, Hq, D]
             if self.use_prefill_kernel:
                 att = ops.prefill_attention(q, kc, vc, slot, start_pos, self.prefix_slot if shared else None,
@@ -611,7 +743,7 @@ class LocalLM:
         h = ops.add_rmsnorm(x, self.w["l0.ln1"], c.eps)
         for i in range(c.layers):
             kc, vc = self.k_cache[i], self.v_cache[i]
-            qkv = F.linear(h, self.w[f"l{i}.wqkv"])
+            qkv = F.linear(h, self.w[f"l{i}.wqkv"], self.w.get(f"l{i}.bqkv"))
             q = ops.rope_kv(qkv, pos_t, slot_t, self.cos_sin, kc, vc, c.n_heads)  # [Ttot, Hq, D]
             att = ops.prefill_attention_varlen(q, kc, vc, offsets, seq_slots, starts, prefix, shared, self.scale)
             o = F.linear(att.view(Ttot, c.n_heads * c.head_dim), self.w[f"l{i}.wo"])
@@ -700,14 +832,16 @@ class LocalLM:
         for i in range(c.layers):
             kc, vc = self.k_cache[i], self.v_cache[i]
             nxt = self.w[f"l{i + 1}.ln1"] if i + 1 < c.layers else self.w["norm_f"]
+            bqkv = self.w.get(f"l{i}.bqkv")
             if big:
                 q = ops.tgemm_rope_kv(h, self.w[f"l{i}.wqkv"], positions, slots, self.cos_sin, kc, vc, c.n_heads,
-                                      self.tg_ws)
+                                      self.tg_ws, bias=bqkv)
             elif wide:
                 q = ops.wgemm_rope_kv(h, self.w[f"l{i}.wqkv"], positions, slots, self.cos_sin, kc, vc, c.n_heads,
-                                      self.wgemm_ws)
+                                      self.wgemm_ws, bias=bqkv)
             else:
-                q = ops.rope_kv(F.linear(h, self.w[f"l{i}.wqkv"]), positions, slots, self.cos_sin, kc, vc, c.n_heads)
+                q = ops.rope_kv(F.linear(h, self.w[f"l{i}.wqkv"], bqkv), positions, slots, self.cos_sin, kc, vc,
+                                c.n_heads)
             att = ops.decode_attention(q, kc, vc, slots, seq_len, self.scale, workspace=self.attn_ws, chunk=chunk,
                                        fork=self.fork_tab,
                                        prefix=self._prefix(i, prefix_rows), splits=splits).view(B, c.n_heads * c.head_dim)
@@ -792,7 +926,8 @@ class LocalLM:
                                               mask_idx, mask_alt, alt_token)
         for i in range(c.layers):
             kc, vc = self.k_cache[i], self.v_cache[i]
-            q = ops.fused_rope_kv(r, self.w[f"l{i}.wqkv"], c.eps, positions, slots, self.cos_sin, kc, vc, c.n_heads)
+            q = ops.fused_rope_kv(r, self.w[f"l{i}.wqkv"], c.eps, positions, slots, self.cos_sin, kc, vc, c.n_heads,
+                                  bias=self.w.get(f"l{i}.bqkv"))
             att = ops.decode_attention(q, kc, vc, slots, seq_len, self.scale, workspace=self.attn_ws, chunk=chunk,
                                        fork=self.fork_tab,
                                        prefix=self._prefix(i, prefix_rows), splits=splits)
@@ -959,7 +1094,8 @@ class LocalLM:
 
     # reference path (pure torch, fp32 math) for numerics tests
     @torch.inference_mode()
-    def reference_logits(self, tokens: Sequence[int]) -> torch.Tensor:
+    def reference_logits(self, tokens: Sequence[int], start_pos: int = 0) -> torch.Tensor:
+        """fp32 logits [T, vocab] of ``tokens`` at positions [start_pos, start_pos + T)."""
         c = self.cfg
         dev = self.device
         w = {k: v.float() for k, v in self.w.items()}
@@ -970,12 +1106,14 @@ class LocalLM:
         def rms(t, g):
             return t * torch.rsqrt(t.pow(2).mean(-1, keepdim=True) + c.eps) * g
 
-        pos = torch.arange(T, device=dev, dtype=torch.int32)
+        pos = torch.arange(start_pos, start_pos + T, device=dev, dtype=torch.int32)
         cs = self.cos_sin
         G = c.n_heads // c.n_kv_heads
         for i in range(c.layers):
             h = rms(x, w[f"l{i}.ln1"])
             qkv = h @ w[f"l{i}.wqkv"].t()
+            if f"l{i}.bqkv" in w:
+                qkv = qkv + w[f"l{i}.bqkv"]
             qkv = qkv.view(T, c.n_heads + 2 * c.n_kv_heads, c.head_dim)
             q = ops.reference.apply_rope(qkv[:, :c.n_heads], pos, cs)
             k = ops.reference.apply_rope(qkv[:, c.n_heads:c.n_heads + c.n_kv_heads], pos, cs)

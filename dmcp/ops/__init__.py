@@ -4,8 +4,8 @@ GPU (HIP) tensors run the hand-written gfx950 kernels of ``dmcp/ops/csrc``
 (:mod:`dmcp.ops.hip`, loaded from the in-tree ``_hipops.so``; a missing
 library is an error, never a silent fallback).  CPU tensors run the fp32
 PyTorch references of :mod:`dmcp.ops.reference` -- that path exists for
-GPU-less unit tests, and only for the ops below that have one; the fused /
-weight-streaming GEMMs are GPU-only and are re-exported from :mod:`.hip`.
+GPU-less unit tests, and only for the ops below that have one; the other
+fused / weight-streaming GEMMs are GPU-only and are re-exported from :mod:`.hip`.
 
 Launch limits and plans (row limits, split counts, workspaces) are defined
 once, in :mod:`.hip`, next to the kernels they describe.
@@ -46,10 +46,11 @@ def _by_device(name: str):
 
 # ops with an fp32 CPU reference: norms, RoPE + KV append, prefill attention,
 # SwiGLU, selection, embedding, the decode step's input gather + first norm,
-# and the MXFP8 prefill path (csrc/pgemm.hip)
+# the MXFP8 prefill path (csrc/pgemm.hip), and the three fused QKV projections
+# (their references define where the optional bias enters)
 DEVICE_OPS = ("add_rmsnorm", "rope_kv", "prefill_attention", "prefill_attention_varlen", "silu_mul",
               "masked_argmax", "lm_head_argmax", "embedding", "decode_embed_norm", "mx_quant", "rmsnorm_mx",
-              "pgemm", "pgemm_resid", "pgemm_swiglu", "pgemm_qkv")
+              "pgemm", "pgemm_resid", "pgemm_swiglu", "pgemm_qkv", "fused_rope_kv", "wgemm_rope_kv", "tgemm_rope_kv")
 for _name in DEVICE_OPS:
     globals()[_name] = _by_device(_name)
 del _name

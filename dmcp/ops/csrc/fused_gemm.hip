@@ -49,6 +49,7 @@ struct FusedGemmArgs {
     void* v_cache;
     int Hq, Hkv, D, max_seq, max_pos, num_slots;
     int kv8;
+    const uint16_t* bias;  // [N] bf16 added to the normalised accumulator before RoPE; nullptr = none
 };
 
 template <int EPI>
@@ -233,6 +234,16 @@ __global__ __launch_bounds__(WK * kWave) void fused_gemm_kernel(FusedGemmArgs a)
             const int D = a.D, half = D / 2;
             const int hh = r0 / D;
             const int d0 = r0 - hh * D + 4 * g;  // < D/2: this lane's 4 dims and their partners d0 + D/2
+            if (a.bias) {  // projection bias (q, k and v heads): columns r0 + 4g + i and their partners
+                float b1[4], b2[4];
+                unpack4(*reinterpret_cast<const uint2*>(a.bias + r0 + 4 * g), b1);
+                unpack4(*reinterpret_cast<const uint2*>(a.bias + r0 + 4 * g + half), b2);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    v[0][i] += b1[i];
+                    v[1][i] += b2[i];
+                }
+            }
             const int p = a.pos[m];
             float o1[4], o2[4];
             if (hh < a.Hq + a.Hkv) {  // q and k heads: rotate-half RoPE
@@ -300,18 +311,19 @@ extern "C" {
 int dmcp_fused_gemm_max_rows() { return 128; }
 
 // epi: 0 = ROPE_KV, 1 = SWIGLU, 2 = RESID, 3 = BF16 (see fused_gemm.hip).
-// wk: waves per block splitting K (1, 2, 4, 8 or 16).  Shapes are validated
+// wk: waves per block splitting K (1, 2, 4, 8 or 16).  bias (ROPE_KV only):
+// [N] bf16 added before RoPE, nullptr = none.  Shapes are validated
 // by the host wrapper (dmcp/ops/hip.py::fused_gemm); the checks here only
 // guard the tiling assumptions.
 int dmcp_fused_gemm(int epi, int wk, const void* x, const void* w, void* out, int M, int K, int N, float eps,
                     int inter, const void* pos, const void* slot, const void* cos_sin, void* q_out, void* k_cache,
                     void* v_cache, int Hq, int Hkv, int D, int max_seq, int max_pos, int num_slots, int kv8,
-                    void* stream) {
+                    void* stream, const void* bias) {
     if (M <= 0) return 0;
     if (M > 128 || K <= 0 || K % 32 != 0 || N <= 0 || !x || !w) return hipErrorInvalidValue;
     FusedGemmArgs a{(const uint16_t*)x, (const uint16_t*)w, (uint16_t*)out, M, K, N, eps, inter,
                     (const int32_t*)pos, (const int32_t*)slot, (const float2*)cos_sin, (uint16_t*)q_out,
-                    k_cache, v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots, kv8};
+                    k_cache, v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots, kv8, (const uint16_t*)bias};
     auto st = (hipStream_t)stream;
     int tiles;
     switch (epi) {

@@ -396,7 +396,8 @@ template <bool KV8>
 __global__ __launch_bounds__(kBlock) void reduce_rope_kv_kernel(
     const float* __restrict__ part, int S, int M, const int32_t* __restrict__ pos, const int32_t* __restrict__ slot,
     const float2* __restrict__ cos_sin, uint16_t* __restrict__ q_out, void* __restrict__ k_cache,
-    void* __restrict__ v_cache, int Hq, int Hkv, int D, int max_seq, int max_pos, int num_slots) {
+    void* __restrict__ v_cache, int Hq, int Hkv, int D, int max_seq, int max_pos, int num_slots,
+    const uint16_t* __restrict__ bias) {
     __shared__ uint4 rowbuf[8192 / 8];
     const int t = blockIdx.x;
     const int N = (Hq + 2 * Hkv) * D;
@@ -404,6 +405,12 @@ __global__ __launch_bounds__(kBlock) void reduce_rope_kv_kernel(
     for (int idx = threadIdx.x; idx < nvec; idx += kBlock) {
         float h[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         sum_slices8(part, S, M, t, N, idx, h);
+        if (bias) {  // projection bias [N] bf16, on the fp32 sum
+            float b[8];
+            unpack8(reinterpret_cast<const uint4*>(bias)[idx], b);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) h[j] += b[j];
+        }
         rowbuf[idx] = pack8(h);
     }
     __syncthreads();
@@ -597,10 +604,12 @@ int dmcp_wgemm_resid_norm(const void* x, const void* w, void* part, void* resid,
 }
 
 // q_out[M, Hq, D] = RoPE(q); k / v appended to the caches; of qkv = x . w^T
-// (w [(Hq + 2 Hkv) D, K]) -- F.linear + rope_kv in one GEMM + one reduction.
+// (w [(Hq + 2 Hkv) D, K]) + bias ([N] bf16, nullptr = none) -- F.linear +
+// rope_kv in one GEMM + one reduction.
 int dmcp_wgemm_rope_kv(const void* x, const void* w, void* part, const void* pos, const void* slot,
                        const void* cos_sin, void* q_out, void* k_cache, void* v_cache, int M, int K, int Hq, int Hkv,
-                       int D, int max_seq, int max_pos, int num_slots, int kv8, int S, int mparts, void* stream) {
+                       int D, int max_seq, int max_pos, int num_slots, int kv8, int S, int mparts, void* stream,
+                       const void* bias) {
     if (M <= 0) return 0;
     const int N = (Hq + 2 * Hkv) * D;
     if (D % 16 != 0 || N > 8192 || !pos || !slot || !cos_sin || !q_out || !k_cache || !v_cache || max_pos <= 0)
@@ -609,14 +618,15 @@ int dmcp_wgemm_rope_kv(const void* x, const void* w, void* part, const void* pos
     if (e != hipSuccess) return e;
     auto st = (hipStream_t)stream;
     auto pp = (const float*)part;
+    auto bb = (const uint16_t*)bias;  // [N] bf16 or nullptr
     if (kv8)
         reduce_rope_kv_kernel<true><<<M, kBlock, 0, st>>>(pp, S, M, (const int32_t*)pos, (const int32_t*)slot,
                                                           (const float2*)cos_sin, (uint16_t*)q_out, k_cache, v_cache,
-                                                          Hq, Hkv, D, max_seq, max_pos, num_slots);
+                                                          Hq, Hkv, D, max_seq, max_pos, num_slots, bb);
     else
         reduce_rope_kv_kernel<false><<<M, kBlock, 0, st>>>(pp, S, M, (const int32_t*)pos, (const int32_t*)slot,
                                                            (const float2*)cos_sin, (uint16_t*)q_out, k_cache,
-                                                           v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots);
+                                                           v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots, bb);
     return hipGetLastError();
 }
 
@@ -639,23 +649,25 @@ int dmcp_reduce_resid_norm(const void* part, int S, void* resid, const void* g, 
 }
 
 // ... and RoPE + q write + KV append of QKV partials [S, M, (Hq + 2 Hkv) D]
+// (+ bias [N] bf16, nullptr = none)
 int dmcp_reduce_rope_kv(const void* part, int S, const void* pos, const void* slot, const void* cos_sin, void* q_out,
                         void* k_cache, void* v_cache, int M, int Hq, int Hkv, int D, int max_seq, int max_pos,
-                        int num_slots, int kv8, void* stream) {
+                        int num_slots, int kv8, void* stream, const void* bias) {
     if (M <= 0) return 0;
     if (!part || S < 1 || D % 16 != 0 || (Hq + 2 * Hkv) * D > 8192 || !pos || !slot || !cos_sin || !q_out ||
         !k_cache || !v_cache || max_pos <= 0)
         return hipErrorInvalidValue;
     auto st = (hipStream_t)stream;
     auto pp = (const float*)part;
+    auto bb = (const uint16_t*)bias;  // [N] bf16 or nullptr
     if (kv8)
         reduce_rope_kv_kernel<true><<<M, kBlock, 0, st>>>(pp, S, M, (const int32_t*)pos, (const int32_t*)slot,
                                                           (const float2*)cos_sin, (uint16_t*)q_out, k_cache, v_cache,
-                                                          Hq, Hkv, D, max_seq, max_pos, num_slots);
+                                                          Hq, Hkv, D, max_seq, max_pos, num_slots, bb);
     else
         reduce_rope_kv_kernel<false><<<M, kBlock, 0, st>>>(pp, S, M, (const int32_t*)pos, (const int32_t*)slot,
                                                            (const float2*)cos_sin, (uint16_t*)q_out, k_cache,
-                                                           v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots);
+                                                           v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots, bb);
     return hipGetLastError();
 }
 

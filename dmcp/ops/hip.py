@@ -27,7 +27,7 @@ _lock = threading.Lock()
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
-ABI_VERSION = 17  # must match dmcp_abi_version() in csrc/dmcp_kernels.hip
+ABI_VERSION = 18  # must match dmcp_abi_version() in csrc/dmcp_kernels.hip
 
 
 class HipOpsError(RuntimeError):
@@ -82,15 +82,16 @@ def lib() -> ctypes.CDLL:
             "dmcp_wgemm_mx": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
             "dmcp_reduce_resid_norm_mx": ([_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp], _i),
             "dmcp_reduce_resid_norm": ([_vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp], _i),
-            "dmcp_reduce_rope_kv": ([_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
+            "dmcp_reduce_rope_kv": ([_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp],
+                                    _i),
             "dmcp_wgemm": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
             "dmcp_tgemm": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp], _i),
             "dmcp_tgemm_probe": ([_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
             "dmcp_wgemm_resid_norm": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp], _i),
             "dmcp_wgemm_rope_kv": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i,
-                                    _i, _i, _vp], _i),
+                                    _i, _i, _vp, _vp], _i),
             "dmcp_fused_gemm": ([_i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i,
-                                 _i, _i, _i, _i, _vp], _i),
+                                 _i, _i, _i, _i, _vp, _vp], _i),
         }
         for name, (args, res) in sigs.items():
             fn = getattr(L, name)
@@ -150,6 +151,15 @@ def _req_out(t: torch.Tensor, dtype: torch.dtype, numel: int, name: str) -> None
     _req(t, dtype, name)
     if t.numel() < numel:
         raise HipOpsError(f"{name}: buffer holds {t.numel()} elements, the kernel writes {numel}")
+
+
+def _req_bias(bias: Optional[torch.Tensor], n: int, name: str) -> None:
+    """An optional projection bias: bf16, one value per output column."""
+    if bias is None:
+        return
+    _req(bias, torch.bfloat16, f"{name}.bias")
+    if bias.numel() != n:
+        raise HipOpsError(f"{name}: bias holds {bias.numel()} elements, the projection has {n} columns")
 
 
 # ---------------------------------------------------------------- wrappers
@@ -682,21 +692,25 @@ def _fused_xw(x: torch.Tensor, w: torch.Tensor, name: str) -> tuple:
 
 def _fused(epi: str, wk: int, x, w, out, M, K, N, eps=0.0, inter=0, pos=None, slot=None, cos_sin=None,
            q_out=None, k_cache=None, v_cache=None, Hq=0, Hkv=0, D=0, max_seq=0, max_pos=0, num_slots=0,
-           kv8=0) -> None:
+           kv8=0, bias=None) -> None:
     if wk not in (4, 8, 16):
         raise HipOpsError(f"fused_gemm: wk must be 4, 8 or 16 (got {wk})")
     _check(lib().dmcp_fused_gemm(FUSED_EPI[epi], wk, _ptr(x), _ptr(w), _ptr(out), M, K, N, float(eps), inter,
                                  _ptr(pos), _ptr(slot), _ptr(cos_sin), _ptr(q_out), _ptr(k_cache), _ptr(v_cache),
-                                 Hq, Hkv, D, max_seq, max_pos, num_slots, kv8, _stream()), f"dmcp_fused_gemm[{epi}]")
+                                 Hq, Hkv, D, max_seq, max_pos, num_slots, kv8, _stream(), _ptr(bias)),
+           f"dmcp_fused_gemm[{epi}]")
 
 
 def fused_rope_kv(x: torch.Tensor, w: torch.Tensor, eps: float, pos: torch.Tensor, slot: torch.Tensor,
                   cos_sin: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int,
-                  q_out: Optional[torch.Tensor] = None, wk: int = 8) -> torch.Tensor:
+                  q_out: Optional[torch.Tensor] = None, wk: int = 8,
+                  bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q = RoPE(rms(x) . w[:Hq*D]^T); RoPE(k) and v appended to the KV cache at
     (slot[m], :, pos[m]) -- the RMSNorm weight must be folded into ``w``.
-    x [M, K]; w [(Hq + 2 Hkv) D, K]; caches [S, Hkv, MAXS, D].  Returns q [M, Hq, D]."""
+    x [M, K]; w [(Hq + 2 Hkv) D, K]; caches [S, Hkv, MAXS, D]; ``bias`` [N]
+    bf16 is added to the normalised fp32 product before RoPE.  Returns q [M, Hq, D]."""
     M, K, N = _fused_xw(x, w, "fused_rope_kv")
+    _req_bias(bias, N, "fused_rope_kv")
     S, Hkv, MAXS, D = k_cache.shape
     kv8 = _req_kv(k_cache, v_cache, "fused_rope_kv")
     _req(pos, torch.int32, "fused_rope_kv.pos")
@@ -711,7 +725,7 @@ def fused_rope_kv(x: torch.Tensor, w: torch.Tensor, eps: float, pos: torch.Tenso
     _req_out(q_out, torch.bfloat16, M * n_q_heads * D, "fused_rope_kv.q_out")
     _fused("rope_kv", wk, x, w, None, M, K, N, eps, pos=pos, slot=slot, cos_sin=cos_sin, q_out=q_out,
            k_cache=k_cache, v_cache=v_cache, Hq=n_q_heads, Hkv=Hkv, D=D, max_seq=MAXS,
-           max_pos=cos_sin.shape[0], num_slots=S, kv8=kv8)
+           max_pos=cos_sin.shape[0], num_slots=S, kv8=kv8, bias=bias)
     return q_out
 
 
@@ -924,11 +938,13 @@ def wgemm_resid_norm(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor, n
 
 def wgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
                   k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, workspace: torch.Tensor,
-                  q_out: Optional[torch.Tensor] = None, splits: int = 0) -> torch.Tensor:
-    """rope_kv(F.linear(x, w), ...) as one split-K GEMM + one reduction per row
-    (RoPE, the q write and the K/V-cache append).  x [M, K] (M <= WGEMM_MAX_ROWS);
-    returns q [M, Hq, D]."""
+                  q_out: Optional[torch.Tensor] = None, splits: int = 0,
+                  bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rope_kv(F.linear(x, w, bias), ...) as one split-K GEMM + one reduction per
+    row (the bias on the fp32 sum, RoPE, the q write and the K/V-cache append).
+    x [M, K] (M <= WGEMM_MAX_ROWS); returns q [M, Hq, D]."""
     M, K, N = _wgemm_args(x, w, "wgemm_rope_kv")
+    _req_bias(bias, N, "wgemm_rope_kv")
     S_, Hkv, MAXS, D = k_cache.shape
     kv8 = _req_kv(k_cache, v_cache, "wgemm_rope_kv")
     _req(pos, torch.int32, "wgemm_rope_kv.pos")
@@ -948,7 +964,8 @@ def wgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: tor
     _req_out(q_out, torch.bfloat16, M * n_q_heads * D, "wgemm_rope_kv.q_out")
     _check(lib().dmcp_wgemm_rope_kv(_ptr(x), _ptr(w), _ptr(workspace), _ptr(pos), _ptr(slot), _ptr(cos_sin),
                                     _ptr(q_out), _ptr(k_cache), _ptr(v_cache), M, K, n_q_heads, Hkv, D, MAXS,
-                                    cos_sin.shape[0], S_, kv8, S, mparts, _stream()), "dmcp_wgemm_rope_kv")
+                                    cos_sin.shape[0], S_, kv8, S, mparts, _stream(), _ptr(bias)),
+           "dmcp_wgemm_rope_kv")
     return q_out
 
 
@@ -1227,7 +1244,7 @@ def wgemm_mx_rope_kv(xq, xs, wq, ws, pos: torch.Tensor, slot: torch.Tensor, cos_
     _req_out(q_out, torch.bfloat16, M * n_q_heads * D, "wgemm_mx_rope_kv.q_out")
     _check(lib().dmcp_reduce_rope_kv(_ptr(workspace), S, _ptr(pos), _ptr(slot), _ptr(cos_sin), _ptr(q_out),
                                      _ptr(k_cache), _ptr(v_cache), M, n_q_heads, Hkv, D, MAXS, cos_sin.shape[0], S_,
-                                     kv8, _stream()), "dmcp_reduce_rope_kv")
+                                     kv8, _stream(), None), "dmcp_reduce_rope_kv")
     return q_out
 
 
@@ -1367,10 +1384,12 @@ def tgemm_resid_norm(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor, n
 
 def tgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
                   k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, workspace: torch.Tensor,
-                  q_out: Optional[torch.Tensor] = None, splits: int = 0) -> torch.Tensor:
-    """rope_kv(F.linear(x, w), ...) as the large-tile split-K GEMM + the fused
-    RoPE / q write / KV-append reduction; returns q [M, Hq, D]."""
+                  q_out: Optional[torch.Tensor] = None, splits: int = 0,
+                  bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rope_kv(F.linear(x, w, bias), ...) as the large-tile split-K GEMM + the
+    fused bias / RoPE / q write / KV-append reduction; returns q [M, Hq, D]."""
     M, K, N = _tgemm_args(x, w, "tgemm_rope_kv")
+    _req_bias(bias, N, "tgemm_rope_kv")
     S_, Hkv, MAXS, D = k_cache.shape
     kv8 = _req_kv(k_cache, v_cache, "tgemm_rope_kv")
     _req(pos, torch.int32, "tgemm_rope_kv.pos")
@@ -1386,7 +1405,7 @@ def tgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: tor
     _req_out(q_out, torch.bfloat16, M * n_q_heads * D, "tgemm_rope_kv.q_out")
     _check(lib().dmcp_reduce_rope_kv(_ptr(workspace), S, _ptr(pos), _ptr(slot), _ptr(cos_sin), _ptr(q_out),
                                      _ptr(k_cache), _ptr(v_cache), M, n_q_heads, Hkv, D, MAXS, cos_sin.shape[0], S_,
-                                     kv8, _stream()), "dmcp_reduce_rope_kv")
+                                     kv8, _stream(), _ptr(bias)), "dmcp_reduce_rope_kv")
     return q_out
 
 

@@ -6,6 +6,7 @@ Signatures mirror :mod:`dmcp.ops.hip`.
 """
 from __future__ import annotations
 
+import math
 from typing import NamedTuple, Optional
 
 import torch
@@ -44,10 +45,64 @@ def kv_encode(x: torch.Tensor, cache_dtype: torch.dtype) -> torch.Tensor:
     return x.to(cache_dtype)
 
 
-def rope_tables(max_pos: int, head_dim: int, theta: float = 10000.0, device=None) -> torch.Tensor:
-    """[max_pos, D/2, 2] float32 (cos, sin) -- viewed as float2 by the kernel."""
+ROPE_TYPES = ("default", "linear", "llama3")
+
+
+def rope_scaling_key(scaling) -> Optional[tuple]:
+    """A checkpoint's ``rope_scaling`` / ``rope_parameters`` dict as the
+    hashable form :class:`dmcp.models.llm.LMConfig` keeps: sorted (key, value)
+    pairs with the type under ``rope_type`` (the legacy key ``type`` is
+    renamed); None for no scaling.  Raises ValueError for a type outside
+    :data:`ROPE_TYPES` or a missing parameter."""
+    if not scaling:
+        return None
+    d = dict(scaling)
+    kind = d.pop("rope_type", None) or d.pop("type", None) or "default"
+    d.pop("type", None)
+    d.pop("rope_theta", None)  # rope_parameters carries theta too; LMConfig.rope_theta holds it
+    if kind not in ROPE_TYPES:
+        raise ValueError(f"rope_type {kind!r} is not supported (supported: {', '.join(ROPE_TYPES)})")
+    if kind == "default":
+        return None
+    need = {"linear": ("factor",),
+            "llama3": ("factor", "low_freq_factor", "high_freq_factor", "original_max_position_embeddings")}[kind]
+    missing = [k for k in need if k not in d]
+    if missing:
+        raise ValueError(f"rope_type {kind!r} needs {', '.join(missing)}")
+    return tuple(sorted([("rope_type", kind)] + [(k, float(d[k])) for k in need]))
+
+
+def rope_inv_freq(head_dim: int, theta: float = 10000.0, scaling=None) -> torch.Tensor:
+    """The rotary pairs' frequencies [D/2] (float64) under ``scaling``: None /
+    "default", "linear" (inv_freq / factor) or "llama3" (pairs of wavelength >
+    orig / low_freq_factor divided by factor, < orig / high_freq_factor
+    unchanged, interpolated between).  The scaling is evaluated in fp32, as
+    the checkpoints' own code does, so the frequencies are the ones the model
+    was trained with to the last bit."""
     half = head_dim // 2
     inv = 1.0 / (theta ** (torch.arange(0, half, dtype=torch.float64) / half))
+    sc = dict(rope_scaling_key(scaling) or ())
+    if not sc:
+        return inv
+    # fp32 from the start, the way the checkpoints' own code builds them
+    f = 1.0 / (theta ** (torch.arange(0, 2 * half, 2, dtype=torch.int64).to(torch.float32) / (2 * half)))
+    if sc["rope_type"] == "linear":
+        return (f / sc["factor"]).to(torch.float64)
+    factor, low, high = sc["factor"], sc["low_freq_factor"], sc["high_freq_factor"]
+    orig = sc["original_max_position_embeddings"]
+    wavelen = 2 * math.pi / f
+    out = torch.where(wavelen > orig / low, f / factor, f)
+    smooth = (orig / wavelen - low) / (high - low)
+    mid = (1 - smooth) * out / factor + smooth * out
+    is_mid = ~(wavelen < orig / high) & ~(wavelen > orig / low)
+    return torch.where(is_mid, mid, out).to(torch.float64)
+
+
+def rope_tables(max_pos: int, head_dim: int, theta: float = 10000.0, device=None, scaling=None) -> torch.Tensor:
+    """[max_pos, D/2, 2] float32 (cos, sin) -- viewed as float2 by the kernel.
+    ``scaling``: a ``rope_scaling`` dict (or its :func:`rope_scaling_key`
+    form) of type "linear" or "llama3"; None = the plain ``theta`` table."""
+    inv = rope_inv_freq(head_dim, theta, scaling)
     ang = torch.arange(max_pos, dtype=torch.float64)[:, None] * inv[None, :]
     return torch.stack([ang.cos(), ang.sin()], dim=-1).to(torch.float32).to(device)
 
@@ -82,6 +137,40 @@ def rope_kv(qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: t
         q_out.copy_(q)
         return q_out
     return q
+
+
+def _linear_f32(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+    y = x.float() @ w.float().t()
+    return y if bias is None else y + bias.float()
+
+
+def fused_rope_kv(x: torch.Tensor, w: torch.Tensor, eps: float, pos: torch.Tensor, slot: torch.Tensor,
+                  cos_sin: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int,
+                  q_out: Optional[torch.Tensor] = None, wk: int = 8,
+                  bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rope_kv(rms(x) . w^T + bias) with the product kept in fp32 up to RoPE
+    (the fused kernel rotates its accumulator); ``wk`` is the kernel's."""
+    xf = x.float()
+    xn = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
+    return rope_kv(_linear_f32(xn, w, bias), pos, slot, cos_sin, k_cache, v_cache, n_q_heads, q_out
+                   ).to(torch.bfloat16)
+
+
+def wgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
+                  k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, workspace=None,
+                  q_out: Optional[torch.Tensor] = None, splits: int = 0,
+                  bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rope_kv(bf16(x . w^T + bias)): the split-K reduction rounds the biased
+    fp32 sum to bf16 before RoPE (what F.linear + rope_kv compute)."""
+    return rope_kv(_linear_f32(x, w, bias).to(torch.bfloat16), pos, slot, cos_sin, k_cache, v_cache, n_q_heads, q_out)
+
+
+def tgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
+                  k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, workspace=None,
+                  q_out: Optional[torch.Tensor] = None, splits: int = 0,
+                  bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The same composition as :func:`wgemm_rope_kv` (one reduction serves both)."""
+    return wgemm_rope_kv(x, w, pos, slot, cos_sin, k_cache, v_cache, n_q_heads, workspace, q_out, splits, bias)
 
 
 class SharedPrefix(NamedTuple):

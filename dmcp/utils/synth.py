@@ -439,7 +439,9 @@ def stack_trace_for(fqcns: List[str], frames: int = 20, seed: int = 11) -> List[
 
 def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int = 32, kv_heads: int = 8,
                      intermediate: int = 8192, vocab: int = 128256, tokenizer: str = "code-bpe-128k",
-                     outliers=(7, 300, 1029, 1800), seed: int = 11, device: str = "cuda") -> str:
+                     outliers=(7, 300, 1029, 1800), seed: int = 11, device: str = "cuda", rope_scaling=None,
+                     qkv_bias: bool = False, model_type: Optional[str] = None, tie_embeddings: bool = False,
+                     head_dim: Optional[int] = None) -> str:
     """A Llama-format checkpoint directory (``config.json``, one
     ``model.safetensors``, ``tokenizer.json``) with *trained-like* random
     weights -- no download exists here: heavy-tailed matrices (a Gaussian
@@ -447,7 +449,15 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
     spread, and a few residual channels (``outliers``) carried at ~100x the
     others and damped by small norm weights, as trained Llama checkpoints
     show.  Llama-3.2-1B geometry by default (2.5 GB), the shipped 128,256-id
-    code BPE as its tokenizer.  The tensors are drawn on ``device``."""
+    code BPE as its tokenizer.  The tensors are drawn on ``device``.
+
+    The defaults write what they always wrote (same seed, same tensors).
+    ``rope_scaling``: a dict written to config.json as is.  ``qkv_bias``: q/k/v
+    projection biases drawn N(0, 2^2) after every other tensor -- a Qwen2
+    checkpoint's layout with values no loader can drop unnoticed, far from
+    fp8 saturation.  ``model_type="qwen2"`` writes the Qwen2 config keys;
+    ``tie_embeddings`` omits ``lm_head.weight``; ``head_dim`` decouples the
+    head width from hidden / heads."""
     import gzip
     import json
 
@@ -455,7 +465,7 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
     from safetensors.torch import save_file
     os.makedirs(root, exist_ok=True)
     g = torch.Generator(device=device).manual_seed(seed)
-    hd = hidden // heads
+    hd = head_dim or hidden // heads
     out = [o for o in outliers if o < hidden]
 
     def heavy(shape, std):
@@ -484,11 +494,32 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
         t[p + "mlp.gate_proj.weight"] = heavy((intermediate, hidden), 0.02)
         t[p + "mlp.up_proj.weight"] = heavy((intermediate, hidden), 0.02)
         t[p + "mlp.down_proj.weight"] = heavy((hidden, intermediate), out_std)
+    if qkv_bias:  # after every existing draw: the other tensors do not depend on it
+        for i in range(layers):
+            p = f"model.layers.{i}."
+            for n, rows in (("q", heads * hd), ("k", kv_heads * hd), ("v", kv_heads * hd)):
+                b = 2.0 * torch.randn(rows, generator=g, device=device)
+                t[p + f"self_attn.{n}_proj.bias"] = b.to(torch.bfloat16).cpu()
+    if tie_embeddings:
+        del t["lm_head.weight"]
     save_file(t, os.path.join(root, "model.safetensors"))
     del t
     cfg = {"vocab_size": vocab, "hidden_size": hidden, "num_hidden_layers": layers, "num_attention_heads": heads,
            "num_key_value_heads": kv_heads, "intermediate_size": intermediate, "rms_norm_eps": 1e-5,
            "rope_theta": 500000.0, "architectures": ["LlamaForCausalLM"]}
+    if model_type == "qwen2":
+        cfg.update({"model_type": "qwen2", "architectures": ["Qwen2ForCausalLM"], "hidden_act": "silu",
+                    "use_sliding_window": False, "attention_dropout": 0.0})
+    elif model_type is not None:
+        cfg["model_type"] = model_type
+    if qkv_bias and model_type != "qwen2":
+        cfg["attention_bias"] = True
+    if head_dim is not None:
+        cfg["head_dim"] = head_dim
+    if tie_embeddings:
+        cfg["tie_word_embeddings"] = True
+    if rope_scaling is not None:
+        cfg["rope_scaling"] = dict(rope_scaling)
     if tokenizer:
         assets = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "models", "assets",
                               tokenizer)

@@ -219,7 +219,7 @@ def main() -> int:
                                                        hip._check(hip.lib().dmcp_reduce_rope_kv(
                                                            hip._ptr(ws), S, hip._ptr(pos), hip._ptr(sl), hip._ptr(cs),
                                                            hip._ptr(qo), hip._ptr(kc), hip._ptr(vc), M, c.n_heads, Hkv,
-                                                           D, 2048, cs.shape[0], 8, 1, hip._stream()), "reduce"))
+                                                           D, 2048, cs.shape[0], 8, 1, hip._stream(), None), "reduce"))
                         else:
                             f = lambda i, S=S, mp=mp: (hip.tgemm_partials(x, Ws[i], ws, splits=S, mparts=mp),  # noqa
                                                        hip._check(hip.lib().dmcp_reduce_resid_norm(
