@@ -1,6 +1,7 @@
-// Shared device helpers of the dmcp gfx950 kernels (dmcp_kernels.hip,
-// fused_gemm.hip): bf16 <-> fp32 packing, wave reductions, MFMA operand
-// types.  Header-only, everything in an anonymous namespace per TU.
+// Shared device helpers of the dmcp gfx950 kernels (every .hip file of this
+// directory): bf16 <-> fp32 packing, wave reductions, MFMA operand
+// types, the LDS-DMA wrapper, fp8 KV and MXFP8 encoding, the split-K slice
+// sum.  Header-only, everything in an anonymous namespace per TU.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -62,6 +63,18 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
     return v;
+}
+
+__device__ __forceinline__ float silu(float g) { return g / (1.f + __expf(-g)); }
+
+// LDS-DMA (global_load_lds_dwordx4): each lane's 16 source bytes land at
+// the wave-uniform LDS base + 16 * lane, with no VGPR round trip; counted on
+// vmcnt like any vector load.
+// AUX: cache-policy bits of the load (2 = nt: streamed, evicted first from L2)
+template <int AUX = 0>
+__device__ __forceinline__ void glds16(const void* src, void* lds_base) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                     (__attribute__((address_space(3))) void*)lds_base, 16, 0, AUX);
 }
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -126,6 +139,16 @@ __device__ __forceinline__ uint2 fp8x4_to_bf16x4(uint32_t v) {
 __device__ __forceinline__ uint4 fp8x8_to_bf16x8(const uint2& v) {
     const uint2 a = fp8x4_to_bf16x4(v.x), b = fp8x4_to_bf16x4(v.y);
     return make_uint4(a.x, a.y, b.x, b.y);
+}
+
+// ---- MXFP8 (e4m3 bytes + one E8M0 exponent per 32 elements)
+// E8M0 exponent of a 32-element block of max |x| = amax: the smallest e with
+// amax / 2^e <= 448 (e4m3's largest normal), clamped to the format
+__device__ __forceinline__ int mx_exp(float amax) {
+    if (!(amax > 0.f)) return 0;
+    int e;
+    frexpf(amax * (1.f / 448.f), &e);  // amax / 448 = f * 2^e, f in [0.5, 1)
+    return e < -127 ? -127 : (e > 127 ? 127 : e);
 }
 
 // byte address of element `off` of a bf16 or fp8 (KV8) cache

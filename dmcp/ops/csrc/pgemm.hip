@@ -94,28 +94,16 @@ struct PEpi {
     int grp;              // M tiles per block-order group (dmcp_pgemm_set_group; 0 = 8)
 };
 
-// LDS-DMA of 16 / 4 / 2 bytes per lane (the size must be a literal)
+// LDS-DMA of 4 / 2 bytes per lane (the size must be a literal; 16: glds16)
 template <int SIZE>
 __device__ __forceinline__ void pglds(const void* src, void* lds_base) {
     auto g = (const __attribute__((address_space(1))) void*)src;
     auto l = (__attribute__((address_space(3))) void*)lds_base;
-    if constexpr (SIZE == 16) __builtin_amdgcn_global_load_lds(g, l, 16, 0, 0);
-    else if constexpr (SIZE == 4) __builtin_amdgcn_global_load_lds(g, l, 4, 0, 0);
+    if constexpr (SIZE == 4) __builtin_amdgcn_global_load_lds(g, l, 4, 0, 0);
     else __builtin_amdgcn_global_load_lds(g, l, 2, 0, 0);
 }
 
 __device__ __forceinline__ int chunks_of(int K) { return K / PBK; }
-
-__device__ __forceinline__ float psilu(float g) { return g / (1.f + __expf(-g)); }
-
-// E8M0 exponent of a 32-element block of max |x| = amax: the smallest e with
-// amax / 2^e <= 448 (e4m3's largest normal), clamped to the format
-__device__ __forceinline__ int mx_exp(float amax) {
-    if (!(amax > 0.f)) return 0;
-    int e;
-    frexpf(amax * (1.f / 448.f), &e);  // amax / 448 = f * 2^e, f in [0.5, 1)
-    return e < -127 ? -127 : (e > 127 ? 127 : e);
-}
 
 // one byte of e4m3 (saturating)
 __device__ __forceinline__ uint8_t to_fp8(float x) {
@@ -208,9 +196,9 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(WV / 4,
     auto issue = [&](int c, int st) {
         uint8_t* base = plds + st * PST_BYTES;
 #pragma unroll
-        for (int i = 0; i < PPW; ++i) pglds<16>(asrc[i] + c * PBK, base + (wv * PPW + i) * 1024);
+        for (int i = 0; i < PPW; ++i) glds16(asrc[i] + c * PBK, base + (wv * PPW + i) * 1024);
 #pragma unroll
-        for (int i = 0; i < PPW; ++i) pglds<16>(wsrc[i] + c * PBK, base + PA_BYTES + (wv * PPW + i) * 1024);
+        for (int i = 0; i < PPW; ++i) glds16(wsrc[i] + c * PBK, base + PA_BYTES + (wv * PPW + i) * 1024);
         if (scl) pglds<2>(ssrc + c * 2, base + PA_BYTES + PB_BYTES + (wv & 3) * 256);
     };
 
@@ -250,8 +238,8 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(WV / 4,
     auto piece = [&](int i, int cc, int st) {
         if constexpr ((PG_PROBE & 1) != 0) return;
         uint8_t* base = plds + st * PST_BYTES;
-        if (i < PPW) pglds<16>(asrc[i] + cc * PBK, base + (wv * PPW + i) * 1024);
-        else if (i < 2 * PPW) pglds<16>(wsrc[i - PPW] + cc * PBK, base + PA_BYTES + (wv * PPW + i - PPW) * 1024);
+        if (i < PPW) glds16(asrc[i] + cc * PBK, base + (wv * PPW + i) * 1024);
+        else if (i < 2 * PPW) glds16(wsrc[i - PPW] + cc * PBK, base + PA_BYTES + (wv * PPW + i - PPW) * 1024);
         else if (scl) pglds<2>(ssrc + cc * 2, base + PA_BYTES + PB_BYTES + (wv & 3) * 256);
     };
     // LDS-DMA instructions of this wave per stage: the counted waits leave
@@ -356,8 +344,8 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(WV / 4,
         auto piece2 = [&](int i, int c2, int slot) {
             uint8_t* base = plds + slot * PST2_BYTES;
             const uint32_t kb = (uint32_t)c2 * PBK2;
-            if (i < PP2) pglds<16>(aq + (a2[i] + kb), base + (wv * PP2 + i) * 1024);
-            else if (i < 2 * PP2) pglds<16>(wq + (w2[i - PP2] + kb), base + PA2_BYTES + (wv * PP2 + i - PP2) * 1024);
+            if (i < PP2) glds16(aq + (a2[i] + kb), base + (wv * PP2 + i) * 1024);
+            else if (i < 2 * PP2) glds16(wq + (w2[i - PP2] + kb), base + PA2_BYTES + (wv * PP2 + i - PP2) * 1024);
             else pglds<4>(as + (s2 + (uint32_t)c2 * 4), base + PA2_BYTES + PB2_BYTES + wv * 256);
         };
         // AR: this stage's A pieces in flight in registers
@@ -645,7 +633,7 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(WV / 4,
                 for (int i = 0; i < 16; ++i) {
                     // gate / up rounded to bf16 as the bf16 GEMM's outputs are
                     const float g = bf2f(f2bf(acc[t][u][i] * sg[i])), uu = bf2f(f2bf(acc[t][u + NU / 2][i] * su[i]));
-                    a[i] = bf2f(f2bf(psilu(g) * uu));
+                    a[i] = bf2f(f2bf(silu(g) * uu));
                     amax = __builtin_fmaxf(amax, __builtin_fabsf(a[i]));
                 }
                 amax = half_swap_max(amax);  // the block's other 16 columns are in lane ^ 32
@@ -833,9 +821,9 @@ __global__ __launch_bounds__(kBlock) void wmx_kernel(
     auto issue = [&](int c, int st) {
         uint8_t* base = lds + st * STB;
 #pragma unroll
-        for (int i = 0; i < WI; ++i) pglds<16>(wsrc[i] + c * PBK, base + (wv * WI + i) * 1024);
+        for (int i = 0; i < WI; ++i) glds16(wsrc[i] + c * PBK, base + (wv * WI + i) * 1024);
 #pragma unroll
-        for (int i = 0; i < XI; ++i) pglds<16>(xsrc[i] + c * PBK, base + W_BYTES + (wv * XI + i) * 1024);
+        for (int i = 0; i < XI; ++i) glds16(xsrc[i] + c * PBK, base + W_BYTES + (wv * XI + i) * 1024);
         pglds<2>(ssrc + c * 2, base + W_BYTES + X_BYTES + wv * 256);
     };
 
@@ -916,7 +904,7 @@ __global__ __launch_bounds__(kBlock) void wmx_kernel(
                 for (int i = 0; i < 16; ++i) {
                     const int jj = nt * (NB / 2) + f * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
                     const float g = bf2f(f2bf(acc[f][t][i] * ws[jj])), uu = bf2f(f2bf(acc[f + NF / 2][t][i] * ws[I + jj]));
-                    a[i] = psilu(g) * uu;
+                    a[i] = silu(g) * uu;
                     amax = __builtin_fmaxf(amax, __builtin_fabsf(a[i]));
                 }
                 amax = half_swap_max(amax);  // the block's other 16 columns are in lane ^ 32
@@ -932,65 +920,6 @@ __global__ __launch_bounds__(kBlock) void wmx_kernel(
                 }
             }
         }
-    }
-}
-
-// split-K reduction + residual add + RMSNorm, output MXFP8 (the next MX
-// GEMM's activation): resid += bf16(sum_s part[s]); h = RMSNorm(resid) * w.
-// One block per row, N % 2048 == 0, N <= 8192.
-template <int VPT>
-__global__ __launch_bounds__(kBlock) void reduce_resid_norm_mx_kernel(const float* __restrict__ part, int S,
-                                                                      uint16_t* __restrict__ resid,
-                                                                      const uint16_t* __restrict__ w,
-                                                                      uint8_t* __restrict__ q, uint8_t* __restrict__ s,
-                                                                      int M, int N, float eps) {
-    const int m = blockIdx.x;
-    uint4* rr = reinterpret_cast<uint4*>(resid + (size_t)m * N);
-    const uint4* wr = reinterpret_cast<const uint4*>(w);
-    float h[VPT][8];
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-        const int idx = threadIdx.x + i * kBlock;
-        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        sum_slices8(part, S, M, m, N, idx, acc);
-        float y[8], r[8];
-        unpack8(pack8(acc), y);  // the GEMM output rounded to bf16, as F.linear's
-        unpack8(rr[idx], r);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) y[j] += r[j];
-        const uint4 packed = pack8(y);
-        rr[idx] = packed;
-        unpack8(packed, h[i]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) ss += h[i][j] * h[i][j];
-    }
-    __shared__ float red[kBlock / kWave];
-    ss = wave_sum(ss);
-    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = ss;
-    __syncthreads();
-    float tot = 0.f;
-#pragma unroll
-    for (int i = 0; i < kBlock / kWave; ++i) tot += red[i];
-    const float inv = rsqrtf(tot / (float)N + eps);
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-        const int idx = threadIdx.x + i * kBlock;
-        float g[8], o[8];
-        unpack8(wr[idx], g);
-        float amax = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            o[j] = h[i][j] * inv * g[j];
-            amax = __builtin_fmaxf(amax, __builtin_fabsf(o[j]));
-        }
-        amax = __builtin_fmaxf(amax, __shfl_xor(amax, 1, kWave));
-        amax = __builtin_fmaxf(amax, __shfl_xor(amax, 2, kWave));
-        const int ex = mx_exp(amax);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = ldexpf(o[j], -ex);
-        reinterpret_cast<uint2*>(q + (size_t)m * N)[idx] = make_uint2(pack_fp8x4(o), pack_fp8x4(o + 4));
-        if ((idx & 3) == 0) s[(size_t)m * (N >> 5) + (idx >> 2)] = (uint8_t)(ex + 127);
     }
 }
 
@@ -1283,26 +1212,6 @@ int dmcp_wgemm_mx(const void* xq, const void* xs, const void* wq, const void* ws
         }
 #undef DMCP_WMX_SW
     }
-    return hipGetLastError();
-}
-
-// resid += bf16(sum of the S partials); RMSNorm(resid) * w -> MXFP8 q / s
-int dmcp_reduce_resid_norm_mx(const void* part, int S, void* resid, const void* w, void* q, void* s, int M, int N,
-                              float eps, void* stream) {
-    if (M <= 0) return 0;
-    if (!part || S < 1 || !resid || !w || !q || !s || N % (8 * kBlock) != 0 || N > 4 * 8 * kBlock)
-        return hipErrorInvalidValue;
-    const int vpt = N / (8 * kBlock);
-    auto st = (hipStream_t)stream;
-    auto pp = (const float*)part;
-    auto rr = (uint16_t*)resid;
-    auto ww = (const uint16_t*)w;
-    auto qq = (uint8_t*)q;
-    auto ss = (uint8_t*)s;
-    if (vpt == 1) reduce_resid_norm_mx_kernel<1><<<M, kBlock, 0, st>>>(pp, S, rr, ww, qq, ss, M, N, eps);
-    else if (vpt == 2) reduce_resid_norm_mx_kernel<2><<<M, kBlock, 0, st>>>(pp, S, rr, ww, qq, ss, M, N, eps);
-    else if (vpt == 3) reduce_resid_norm_mx_kernel<3><<<M, kBlock, 0, st>>>(pp, S, rr, ww, qq, ss, M, N, eps);
-    else reduce_resid_norm_mx_kernel<4><<<M, kBlock, 0, st>>>(pp, S, rr, ww, qq, ss, M, N, eps);
     return hipGetLastError();
 }
 

@@ -32,8 +32,8 @@
 //     tile at ~23 KB/us and its activation rows at ~42 KB/us through the
 //     same load path, t ~= W_block / 23 + X_block / 42 (KB, us); 64 / 128
 //     weight rows x the M part already minimise that for ~256 blocks;
-//   * split-K (S > 1) writes fp32 partials, reduced by the fused consumers
-//     below (residual + RMSNorm of the next op; RoPE + KV-cache append);
+//   * split-K (S > 1) writes fp32 partials, reduced by splitk_reduce.hip's
+//     fused consumers (residual + RMSNorm of the next op; RoPE + KV append);
 //     MODE_SWIGLU writes silu(gate) * up directly (no gate/up activation in
 //     HBM, no SwiGLU launch);
 //   * MODE_ARGMAX is the LM head + the grammar-masked greedy selection: each
@@ -48,18 +48,6 @@ namespace {
 
 constexpr int kKC = 64;  // K per LDS stage
 constexpr int MODE_BF16 = 0, MODE_PART = 1, MODE_SWIGLU = 2, MODE_ARGMAX = 3;
-
-__device__ __forceinline__ float silu_f(float g) { return g / (1.f + __expf(-g)); }
-
-// LDS-DMA (global_load_lds_dwordx4): each lane's 16 source bytes land at
-// the wave-uniform LDS base + 16 * lane, with no VGPR round trip; counted on
-// vmcnt like any vector load.
-// AUX: cache-policy bits of the load (2 = nt: streamed, evicted first from L2)
-template <int AUX = 0>
-__device__ __forceinline__ void glds16(const void* src, uint4* lds_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_base, 16, 0, AUX);
-}
 
 template <int NB, int MT, int MR, int MODE, int ST, int AUXW = 0>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) void wgemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
@@ -274,7 +262,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {  // gate / up rounded to bf16 as the unfused GEMM output is
                     const float gg = bf2f(f2bf(acc[f][t][i])), uu = bf2f(f2bf(acc[f + NF / 2][t][i]));
-                    o[i] = silu_f(gg) * uu;
+                    o[i] = silu(gg) * uu;
                 }
                 *reinterpret_cast<uint2*>(y + (size_t)m * I + n0h + 16 * f + 4 * g) = pack4(o);
             }
@@ -291,180 +279,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
                 *reinterpret_cast<uint2*>(y + (size_t)m * N + n0 + 16 * f + 4 * g) = pack4(o);
             }
         }
-    }
-}
-
-// split-K slices whose partials the reductions below load at once
-constexpr int RSU = 4;
-
-// split-K reduction + residual add + RMSNorm of the next op (one block per
-// row): resid += bf16(sum_s part[s]); out = RMSNorm(resid) * gw.  The GEMM
-// output is rounded to bf16 before the add and the stream after it (what
-// F.linear + add_rmsnorm compute).
-template <int VPT>
-__global__ __launch_bounds__(kBlock) void reduce_resid_norm_kernel(const float* __restrict__ part, int S,
-                                                                   uint16_t* __restrict__ resid,
-                                                                   const uint16_t* __restrict__ gw,
-                                                                   uint16_t* __restrict__ out, int M, int N,
-                                                                   float eps) {
-    const int m = blockIdx.x;
-    const int nvec = N >> 3;
-    float h[VPT][8];
-    uint4 rv[VPT], wv[VPT];
-    uint4* rr = reinterpret_cast<uint4*>(resid + (size_t)m * N);
-    const uint4* wr = reinterpret_cast<const uint4*>(gw);
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-        const int idx = threadIdx.x + i * kBlock;
-        if (idx < nvec) {
-            rv[i] = rr[idx];
-            wv[i] = wr[idx];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) h[i][j] = 0.f;
-    }
-    // the partials of RSU slices in flight at once (a plain loop over s waited
-    // for each slice's loads before issuing the next: S serial round trips)
-    for (int s0 = 0; s0 < S; s0 += RSU) {
-        float4 a[RSU][VPT], b[RSU][VPT];
-#pragma unroll
-        for (int j = 0; j < RSU; ++j) {
-            const float4* pp = reinterpret_cast<const float4*>(part + ((size_t)min(s0 + j, S - 1) * M + m) * N);
-#pragma unroll
-            for (int i = 0; i < VPT; ++i) {
-                const int idx = min(threadIdx.x + i * kBlock, nvec - 1);
-                a[j][i] = pp[2 * idx];
-                b[j][i] = pp[2 * idx + 1];
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < RSU; ++j) {
-            const float u = s0 + j < S ? 1.f : 0.f;  // branch-free: a branch let the loads sink to their uses
-#pragma unroll
-            for (int i = 0; i < VPT; ++i) {
-                h[i][0] = fmaf(u, a[j][i].x, h[i][0]); h[i][1] = fmaf(u, a[j][i].y, h[i][1]);
-                h[i][2] = fmaf(u, a[j][i].z, h[i][2]); h[i][3] = fmaf(u, a[j][i].w, h[i][3]);
-                h[i][4] = fmaf(u, b[j][i].x, h[i][4]); h[i][5] = fmaf(u, b[j][i].y, h[i][5]);
-                h[i][6] = fmaf(u, b[j][i].z, h[i][6]); h[i][7] = fmaf(u, b[j][i].w, h[i][7]);
-            }
-        }
-    }
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-        const int idx = threadIdx.x + i * kBlock;
-        if (idx < nvec) {
-            float yv[8], r[8];
-            unpack8(pack8(h[i]), yv);
-            unpack8(rv[i], r);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) yv[j] += r[j];
-            const uint4 packed = pack8(yv);
-            rr[idx] = packed;
-            unpack8(packed, h[i]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) ss += h[i][j] * h[i][j];
-        }
-    }
-    __shared__ float red[kBlock / kWave];
-    ss = wave_sum(ss);
-    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = ss;
-    __syncthreads();
-    float tot = 0.f;
-#pragma unroll
-    for (int i = 0; i < kBlock / kWave; ++i) tot += red[i];
-    const float inv = rsqrtf(tot / (float)N + eps);
-    uint4* orow = reinterpret_cast<uint4*>(out + (size_t)m * N);
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-        const int idx = threadIdx.x + i * kBlock;
-        if (idx < nvec) {
-            float gv[8], o[8];
-            unpack8(wv[i], gv);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = h[i][j] * inv * gv[j];
-            orow[idx] = pack8(o);
-        }
-    }
-}
-
-// split-K reduction of the QKV projection + rotate-half RoPE on q and k, q
-// written out, k / v appended to the KV cache (bf16, or KV8 fp8 e4m3) at
-// (slot[t], :, pos[t], :) -- dmcp_kernels.hip::rope_kv_kernel over an LDS row
-// of the bf16-rounded sum (what F.linear + rope_kv compute).
-template <bool KV8>
-__global__ __launch_bounds__(kBlock) void reduce_rope_kv_kernel(
-    const float* __restrict__ part, int S, int M, const int32_t* __restrict__ pos, const int32_t* __restrict__ slot,
-    const float2* __restrict__ cos_sin, uint16_t* __restrict__ q_out, void* __restrict__ k_cache,
-    void* __restrict__ v_cache, int Hq, int Hkv, int D, int max_seq, int max_pos, int num_slots,
-    const uint16_t* __restrict__ bias) {
-    __shared__ uint4 rowbuf[8192 / 8];
-    const int t = blockIdx.x;
-    const int N = (Hq + 2 * Hkv) * D;
-    const int nvec = N >> 3;
-    for (int idx = threadIdx.x; idx < nvec; idx += kBlock) {
-        float h[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        sum_slices8(part, S, M, t, N, idx, h);
-        if (bias) {  // projection bias [N] bf16, on the fp32 sum
-            float b[8];
-            unpack8(reinterpret_cast<const uint4*>(bias)[idx], b);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) h[j] += b[j];
-        }
-        rowbuf[idx] = pack8(h);
-    }
-    __syncthreads();
-    const uint16_t* row = reinterpret_cast<const uint16_t*>(rowbuf);
-    const int p = pos[t];
-    const int sl = slot[t];
-    const bool write_cache = (p >= 0 && p < max_seq && sl >= 0 && sl < num_slots);
-    const int half = D >> 1;
-    const int quads = half >> 2;
-    const float2* cs = cos_sin + (size_t)min(max(p, 0), max_pos - 1) * half;
-    const int nunits = (Hq + Hkv) * quads;
-    for (int uu = threadIdx.x; uu < nunits; uu += kBlock) {
-        const int hh = uu / quads;
-        const int d0 = (uu - hh * quads) * 4;
-        const uint16_t* src = row + (size_t)hh * D;
-        float x1[4], x2[4], o1[4], o2[4];
-        unpack4(*reinterpret_cast<const uint2*>(src + d0), x1);
-        unpack4(*reinterpret_cast<const uint2*>(src + half + d0), x2);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float2 c = cs[d0 + j];
-            o1[j] = x1[j] * c.x - x2[j] * c.y;
-            o2[j] = x2[j] * c.x + x1[j] * c.y;
-        }
-        if (hh < Hq) {
-            uint16_t* dst = q_out + ((size_t)t * Hq + hh) * D;
-            *reinterpret_cast<uint2*>(dst + d0) = pack4(o1);
-            *reinterpret_cast<uint2*>(dst + half + d0) = pack4(o2);
-            continue;
-        }
-        if (!write_cache) continue;
-        const size_t kofs = (((size_t)sl * Hkv + (hh - Hq)) * max_seq + p) * D;
-        if constexpr (KV8) {
-            uint8_t* dst = static_cast<uint8_t*>(k_cache) + kofs;
-            *reinterpret_cast<uint32_t*>(dst + d0) = pack_fp8x4_bf16r(o1);
-            *reinterpret_cast<uint32_t*>(dst + half + d0) = pack_fp8x4_bf16r(o2);
-        } else {
-            uint16_t* dst = static_cast<uint16_t*>(k_cache) + kofs;
-            *reinterpret_cast<uint2*>(dst + d0) = pack4(o1);
-            *reinterpret_cast<uint2*>(dst + half + d0) = pack4(o2);
-        }
-    }
-    if (!write_cache) return;
-    const int vvec = (Hkv * D) >> 3;
-    const uint4* vsrc = rowbuf + (((Hq + Hkv) * D) >> 3);
-    for (int uu = threadIdx.x; uu < vvec; uu += kBlock) {
-        const int e = uu << 3;
-        const int kh = e / D;
-        const int d = e - kh * D;
-        const size_t vofs = (((size_t)sl * Hkv + kh) * max_seq + p) * D + d;
-        if constexpr (KV8)
-            *reinterpret_cast<uint2*>(static_cast<uint8_t*>(v_cache) + vofs) = bf16x8_to_fp8x8(vsrc[uu]);
-        else
-            *reinterpret_cast<uint4*>(static_cast<uint16_t*>(v_cache) + vofs) = vsrc[uu];
     }
 }
 
@@ -580,94 +394,6 @@ int dmcp_lm_head_argmax(const void* x, const void* w, const void* masks, const v
     if (e != hipSuccess) return e;
     argmax_pairs_kernel<<<(M + kBlock / kWave - 1) / (kBlock / kWave), kBlock, 0, st>>>(
         (const float2*)best, ntiles, M, (int32_t*)ids);
-    return hipGetLastError();
-}
-
-// resid[M, N] += bf16(x . w^T); out = RMSNorm(resid) * g  (split-K GEMM +
-// fused reduction; part: fp32 workspace of S * M * N).
-int dmcp_wgemm_resid_norm(const void* x, const void* w, void* part, void* resid, const void* g, void* out, int M,
-                          int K, int N, int S, int mparts, float eps, void* stream) {
-    if (M <= 0) return 0;
-    if (!resid || !g || !out || N % 8 != 0 || N > 8 * 4 * kBlock) return hipErrorInvalidValue;
-    hipError_t e = (hipError_t)dmcp_wgemm(x, w, nullptr, part, M, N, K, S, mparts, 1, 0, stream);
-    if (e != hipSuccess) return e;
-    auto st = (hipStream_t)stream;
-    const int vpt = (N / 8 + kBlock - 1) / kBlock;
-    auto pp = (const float*)part;
-    auto rr = (uint16_t*)resid;
-    auto gg = (const uint16_t*)g;
-    auto oo = (uint16_t*)out;
-    if (vpt == 1) reduce_resid_norm_kernel<1><<<M, kBlock, 0, st>>>(pp, S, rr, gg, oo, M, N, eps);
-    else if (vpt == 2) reduce_resid_norm_kernel<2><<<M, kBlock, 0, st>>>(pp, S, rr, gg, oo, M, N, eps);
-    else reduce_resid_norm_kernel<4><<<M, kBlock, 0, st>>>(pp, S, rr, gg, oo, M, N, eps);
-    return hipGetLastError();
-}
-
-// q_out[M, Hq, D] = RoPE(q); k / v appended to the caches; of qkv = x . w^T
-// (w [(Hq + 2 Hkv) D, K]) + bias ([N] bf16, nullptr = none) -- F.linear +
-// rope_kv in one GEMM + one reduction.
-int dmcp_wgemm_rope_kv(const void* x, const void* w, void* part, const void* pos, const void* slot,
-                       const void* cos_sin, void* q_out, void* k_cache, void* v_cache, int M, int K, int Hq, int Hkv,
-                       int D, int max_seq, int max_pos, int num_slots, int kv8, int S, int mparts, void* stream,
-                       const void* bias) {
-    if (M <= 0) return 0;
-    const int N = (Hq + 2 * Hkv) * D;
-    if (D % 16 != 0 || N > 8192 || !pos || !slot || !cos_sin || !q_out || !k_cache || !v_cache || max_pos <= 0)
-        return hipErrorInvalidValue;
-    hipError_t e = (hipError_t)dmcp_wgemm(x, w, nullptr, part, M, N, K, S, mparts, 1, 0, stream);
-    if (e != hipSuccess) return e;
-    auto st = (hipStream_t)stream;
-    auto pp = (const float*)part;
-    auto bb = (const uint16_t*)bias;  // [N] bf16 or nullptr
-    if (kv8)
-        reduce_rope_kv_kernel<true><<<M, kBlock, 0, st>>>(pp, S, M, (const int32_t*)pos, (const int32_t*)slot,
-                                                          (const float2*)cos_sin, (uint16_t*)q_out, k_cache, v_cache,
-                                                          Hq, Hkv, D, max_seq, max_pos, num_slots, bb);
-    else
-        reduce_rope_kv_kernel<false><<<M, kBlock, 0, st>>>(pp, S, M, (const int32_t*)pos, (const int32_t*)slot,
-                                                           (const float2*)cos_sin, (uint16_t*)q_out, k_cache,
-                                                           v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots, bb);
-    return hipGetLastError();
-}
-
-// The split-K reductions alone, for partials written by another GEMM (the MX
-// fp8 decode GEMM of pgemm.hip): resid += bf16(sum part); out = RMSNorm * g.
-int dmcp_reduce_resid_norm(const void* part, int S, void* resid, const void* g, void* out, int M, int N, float eps,
-                           void* stream) {
-    if (M <= 0) return 0;
-    if (!part || S < 1 || !resid || !g || !out || N % 8 != 0 || N > 8 * 4 * kBlock) return hipErrorInvalidValue;
-    auto st = (hipStream_t)stream;
-    const int vpt = (N / 8 + kBlock - 1) / kBlock;
-    auto pp = (const float*)part;
-    auto rr = (uint16_t*)resid;
-    auto gg = (const uint16_t*)g;
-    auto oo = (uint16_t*)out;
-    if (vpt == 1) reduce_resid_norm_kernel<1><<<M, kBlock, 0, st>>>(pp, S, rr, gg, oo, M, N, eps);
-    else if (vpt == 2) reduce_resid_norm_kernel<2><<<M, kBlock, 0, st>>>(pp, S, rr, gg, oo, M, N, eps);
-    else reduce_resid_norm_kernel<4><<<M, kBlock, 0, st>>>(pp, S, rr, gg, oo, M, N, eps);
-    return hipGetLastError();
-}
-
-// ... and RoPE + q write + KV append of QKV partials [S, M, (Hq + 2 Hkv) D]
-// (+ bias [N] bf16, nullptr = none)
-int dmcp_reduce_rope_kv(const void* part, int S, const void* pos, const void* slot, const void* cos_sin, void* q_out,
-                        void* k_cache, void* v_cache, int M, int Hq, int Hkv, int D, int max_seq, int max_pos,
-                        int num_slots, int kv8, void* stream, const void* bias) {
-    if (M <= 0) return 0;
-    if (!part || S < 1 || D % 16 != 0 || (Hq + 2 * Hkv) * D > 8192 || !pos || !slot || !cos_sin || !q_out ||
-        !k_cache || !v_cache || max_pos <= 0)
-        return hipErrorInvalidValue;
-    auto st = (hipStream_t)stream;
-    auto pp = (const float*)part;
-    auto bb = (const uint16_t*)bias;  // [N] bf16 or nullptr
-    if (kv8)
-        reduce_rope_kv_kernel<true><<<M, kBlock, 0, st>>>(pp, S, M, (const int32_t*)pos, (const int32_t*)slot,
-                                                          (const float2*)cos_sin, (uint16_t*)q_out, k_cache, v_cache,
-                                                          Hq, Hkv, D, max_seq, max_pos, num_slots, bb);
-    else
-        reduce_rope_kv_kernel<false><<<M, kBlock, 0, st>>>(pp, S, M, (const int32_t*)pos, (const int32_t*)slot,
-                                                           (const float2*)cos_sin, (uint16_t*)q_out, k_cache,
-                                                           v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots, bb);
     return hipGetLastError();
 }
 

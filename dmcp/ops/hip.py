@@ -12,10 +12,11 @@ by :mod:`dmcp.ops` (CPU unit tests only).
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import math
 import os
 import threading
-from typing import Optional
+from typing import Callable, Optional
 
 import numpy as np
 import torch
@@ -27,7 +28,7 @@ _lock = threading.Lock()
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
-ABI_VERSION = 18  # must match dmcp_abi_version() in csrc/dmcp_kernels.hip
+ABI_VERSION = 19  # must match dmcp_abi_version() in csrc/dmcp_kernels.hip
 
 
 class HipOpsError(RuntimeError):
@@ -87,9 +88,6 @@ def lib() -> ctypes.CDLL:
             "dmcp_wgemm": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
             "dmcp_tgemm": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp], _i),
             "dmcp_tgemm_probe": ([_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
-            "dmcp_wgemm_resid_norm": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp], _i),
-            "dmcp_wgemm_rope_kv": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i,
-                                    _i, _i, _vp, _vp], _i),
             "dmcp_fused_gemm": ([_i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i,
                                  _i, _i, _i, _i, _vp, _vp], _i),
         }
@@ -809,16 +807,21 @@ def wgemm_plan(M: int, N: int, K: int, swiglu: bool = False, target_blocks: int 
     return S, mparts
 
 
-def _wgemm_args(x: torch.Tensor, w: torch.Tensor, name: str) -> tuple:
+def _gemm_args(x: torch.Tensor, w: torch.Tensor, name: str, max_rows: int, nb: int) -> tuple:
+    """bf16 x [M, K] / w [N, K] of a decode GEMM of up to ``max_rows`` rows and ``nb``-row weight tiles."""
     _req(x, torch.bfloat16, f"{name}.x")
     _req(w, torch.bfloat16, f"{name}.w")
     if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
         raise HipOpsError(f"{name}: x {tuple(x.shape)} / w {tuple(w.shape)} are not [M, K] / [N, K]")
     M, K = x.shape
     N = w.shape[0]
-    if not 1 <= M <= WGEMM_MAX_ROWS or K % 64 or N % 64:
-        raise HipOpsError(f"{name}: needs 1 <= M <= {WGEMM_MAX_ROWS}, K % 64 == 0, N % 64 == 0 (M={M} K={K} N={N})")
+    if not 1 <= M <= max_rows or K % 64 or N <= 0 or N % nb:
+        raise HipOpsError(f"{name}: needs 1 <= M <= {max_rows}, K % 64 == 0, N % {nb} == 0 (M={M} K={K} N={N})")
     return M, K, N
+
+
+def _wgemm_args(x: torch.Tensor, w: torch.Tensor, name: str) -> tuple:
+    return _gemm_args(x, w, name, WGEMM_MAX_ROWS, 64)
 
 
 def lm_head_supported(vocab: int, hidden: int) -> bool:
@@ -902,15 +905,7 @@ def wgemm_swiglu(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] =
 
 def wgemm_partials(x: torch.Tensor, w: torch.Tensor, workspace: torch.Tensor, splits: int = 0) -> int:
     """fp32 split-K partials of x . w^T into ``workspace`` [S, M, N]; returns S."""
-    M, K, N = _wgemm_args(x, w, "wgemm_partials")
-    S, mparts = wgemm_plan(M, N, K)
-    S = splits or S
-    if K % (64 * S):
-        raise HipOpsError(f"wgemm_partials: K={K} does not split into {S} slices of whole 64-deep chunks")
-    _wgemm_ws(workspace, S * M * N, "wgemm_partials")
-    _check(lib().dmcp_wgemm(_ptr(x), _ptr(w), None, _ptr(workspace), M, N, K, S, mparts, 1, 0, _stream()),
-           "dmcp_wgemm[partials]")
-    return S
+    return _partials(_WGEMM, (x, w), workspace, "wgemm_partials", splits)
 
 
 def wgemm_resid_norm(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor, norm_w: torch.Tensor, eps: float,
@@ -918,22 +913,7 @@ def wgemm_resid_norm(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor, n
     """residual += bf16(x . w^T) (in place); returns RMSNorm(residual) * norm_w
     -- F.linear + add_rmsnorm as one split-K GEMM + one reduction per row that
     adds the residual and normalises.  x [M, K] (M <= WGEMM_MAX_ROWS), w [N, K]."""
-    M, K, N = _wgemm_args(x, w, "wgemm_resid_norm")
-    _req(residual, torch.bfloat16, "wgemm_resid_norm.residual")
-    _req(norm_w, torch.bfloat16, "wgemm_resid_norm.norm_w")
-    if tuple(residual.shape) != (M, N) or norm_w.numel() != N or N > 8192:
-        raise HipOpsError("wgemm_resid_norm: residual / norm weight shape mismatch")
-    S, mparts = wgemm_plan(M, N, K)
-    S = splits or S
-    if K % (64 * S):
-        raise HipOpsError(f"wgemm_resid_norm: K={K} does not split into {S} slices")
-    _wgemm_ws(workspace, S * M * N, "wgemm_resid_norm")
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-    _req_out(out, torch.bfloat16, M * N, "wgemm_resid_norm.out")
-    _check(lib().dmcp_wgemm_resid_norm(_ptr(x), _ptr(w), _ptr(workspace), _ptr(residual), _ptr(norm_w), _ptr(out),
-                                       M, K, N, S, mparts, float(eps), _stream()), "dmcp_wgemm_resid_norm")
-    return out
+    return _resid_norm(_WGEMM, (x, w), residual, norm_w, eps, workspace, "wgemm_resid_norm", out, splits)
 
 
 def wgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
@@ -943,30 +923,8 @@ def wgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: tor
     """rope_kv(F.linear(x, w, bias), ...) as one split-K GEMM + one reduction per
     row (the bias on the fp32 sum, RoPE, the q write and the K/V-cache append).
     x [M, K] (M <= WGEMM_MAX_ROWS); returns q [M, Hq, D]."""
-    M, K, N = _wgemm_args(x, w, "wgemm_rope_kv")
-    _req_bias(bias, N, "wgemm_rope_kv")
-    S_, Hkv, MAXS, D = k_cache.shape
-    kv8 = _req_kv(k_cache, v_cache, "wgemm_rope_kv")
-    _req(pos, torch.int32, "wgemm_rope_kv.pos")
-    _req(slot, torch.int32, "wgemm_rope_kv.slot")
-    _req(cos_sin, torch.float32, "wgemm_rope_kv.cos_sin")
-    if v_cache.shape != k_cache.shape or N != (n_q_heads + 2 * Hkv) * D or D % 16 or N > 8192:
-        raise HipOpsError(f"wgemm_rope_kv: w {tuple(w.shape)} does not match Hq={n_q_heads} / kv {tuple(k_cache.shape)}")
-    if pos.numel() != M or slot.numel() != M or cos_sin.dim() != 3 or tuple(cos_sin.shape[1:]) != (D // 2, 2):
-        raise HipOpsError("wgemm_rope_kv: pos/slot/cos_sin shape mismatch")
-    S, mparts = wgemm_plan(M, N, K)
-    S = splits or S
-    if K % (64 * S):
-        raise HipOpsError(f"wgemm_rope_kv: K={K} does not split into {S} slices")
-    _wgemm_ws(workspace, S * M * N, "wgemm_rope_kv")
-    if q_out is None:
-        q_out = torch.empty((M, n_q_heads, D), dtype=torch.bfloat16, device=x.device)
-    _req_out(q_out, torch.bfloat16, M * n_q_heads * D, "wgemm_rope_kv.q_out")
-    _check(lib().dmcp_wgemm_rope_kv(_ptr(x), _ptr(w), _ptr(workspace), _ptr(pos), _ptr(slot), _ptr(cos_sin),
-                                    _ptr(q_out), _ptr(k_cache), _ptr(v_cache), M, K, n_q_heads, Hkv, D, MAXS,
-                                    cos_sin.shape[0], S_, kv8, S, mparts, _stream(), _ptr(bias)),
-           "dmcp_wgemm_rope_kv")
-    return q_out
+    return _rope_kv(_WGEMM, (x, w), pos, slot, cos_sin, k_cache, v_cache, n_q_heads, workspace, "wgemm_rope_kv",
+                    q_out, splits, bias)
 
 
 def wgemm_workspace(rows: int, n_max: int, device) -> torch.Tensor:
@@ -1171,15 +1129,7 @@ def _wmx_args(xq, xs, wq, ws, name):
 def wgemm_mx_partials(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor,
                       workspace: torch.Tensor, splits: int = 0) -> int:
     """fp32 split-K partials [S, M, N] of MXFP8 x . (e4m3 w * ws)^T; returns S."""
-    M, K, N = _wmx_args(xq, xs, wq, ws, "wgemm_mx_partials")
-    S, mparts = wmx_plan(M, N, K)
-    S = splits or S
-    if K % (64 * S):
-        raise HipOpsError(f"wgemm_mx_partials: K={K} does not split into {S} slices")
-    _wgemm_ws(workspace, S * M * N, "wgemm_mx_partials")
-    _check(lib().dmcp_wgemm_mx(_ptr(xq), _ptr(xs), _ptr(wq), _ptr(ws), _ptr(workspace), None, None, M, N, K, S,
-                               mparts, 1, 0, _stream()), "dmcp_wgemm_mx[partials]")
-    return S
+    return _partials(_WMX, (xq, xs, wq, ws), workspace, "wgemm_mx_partials", splits)
 
 
 def wgemm_mx_swiglu(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor,
@@ -1203,49 +1153,15 @@ def wgemm_mx_resid_norm(xq, xs, wq, ws, residual: torch.Tensor, norm_w: torch.Te
                         workspace: torch.Tensor, mx: bool = True, out: Optional[tuple] = None):
     """residual += bf16(x . w^T); returns RMSNorm(residual) * norm_w as MXFP8
     (q, s) -- or, ``mx=False``, as bf16 (the last layer: the LM head's input)."""
-    M, K, N = _wmx_args(xq, xs, wq, ws, "wgemm_mx_resid_norm")
-    _req(residual, torch.bfloat16, "wgemm_mx_resid_norm.residual")
-    _req(norm_w, torch.bfloat16, "wgemm_mx_resid_norm.norm_w")
-    if tuple(residual.shape) != (M, N) or norm_w.numel() != N or N % 2048 or N > 8192:
-        raise HipOpsError("wgemm_mx_resid_norm: residual / norm weight shape mismatch (N % 2048 == 0, <= 8192)")
-    S = wgemm_mx_partials(xq, xs, wq, ws, workspace)
-    if not mx:
-        h = torch.empty((M, N), dtype=torch.bfloat16, device=xq.device) if out is None else out
-        _req_out(h, torch.bfloat16, M * N, "wgemm_mx_resid_norm.out")
-        _check(lib().dmcp_reduce_resid_norm(_ptr(workspace), S, _ptr(residual), _ptr(norm_w), _ptr(h), M, N,
-                                            float(eps), _stream()), "dmcp_reduce_resid_norm")
-        return h
-    q, s = out if out is not None else (torch.empty((M, N), dtype=torch.uint8, device=xq.device),
-                                        torch.empty((M, N // 32), dtype=torch.uint8, device=xq.device))
-    _req_out(q, torch.uint8, M * N, "wgemm_mx_resid_norm.q")
-    _req_out(s, torch.uint8, M * N // 32, "wgemm_mx_resid_norm.s")
-    _check(lib().dmcp_reduce_resid_norm_mx(_ptr(workspace), S, _ptr(residual), _ptr(norm_w), _ptr(q), _ptr(s), M, N,
-                                           float(eps), _stream()), "dmcp_reduce_resid_norm_mx")
-    return q, s
+    return _resid_norm(_WMX, (xq, xs, wq, ws), residual, norm_w, eps, workspace, "wgemm_mx_resid_norm", out, mx=mx)
 
 
 def wgemm_mx_rope_kv(xq, xs, wq, ws, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
                      k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, workspace: torch.Tensor,
                      q_out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """rope_kv(x . w^T) on the MX decode GEMM: q [M, Hq, D] returned, K/V appended."""
-    M, K, N = _wmx_args(xq, xs, wq, ws, "wgemm_mx_rope_kv")
-    S_, Hkv, MAXS, D = k_cache.shape
-    kv8 = _req_kv(k_cache, v_cache, "wgemm_mx_rope_kv")
-    _req(pos, torch.int32, "wgemm_mx_rope_kv.pos")
-    _req(slot, torch.int32, "wgemm_mx_rope_kv.slot")
-    _req(cos_sin, torch.float32, "wgemm_mx_rope_kv.cos_sin")
-    if v_cache.shape != k_cache.shape or N != (n_q_heads + 2 * Hkv) * D or D % 16 or N > 8192:
-        raise HipOpsError(f"wgemm_mx_rope_kv: w {tuple(wq.shape)} does not match Hq={n_q_heads} / kv "
-                          f"{tuple(k_cache.shape)}")
-    if pos.numel() != M or slot.numel() != M or cos_sin.dim() != 3 or tuple(cos_sin.shape[1:]) != (D // 2, 2):
-        raise HipOpsError("wgemm_mx_rope_kv: pos/slot/cos_sin shape mismatch")
-    S = wgemm_mx_partials(xq, xs, wq, ws, workspace)
-    q_out = torch.empty((M, n_q_heads, D), dtype=torch.bfloat16, device=xq.device) if q_out is None else q_out
-    _req_out(q_out, torch.bfloat16, M * n_q_heads * D, "wgemm_mx_rope_kv.q_out")
-    _check(lib().dmcp_reduce_rope_kv(_ptr(workspace), S, _ptr(pos), _ptr(slot), _ptr(cos_sin), _ptr(q_out),
-                                     _ptr(k_cache), _ptr(v_cache), M, n_q_heads, Hkv, D, MAXS, cos_sin.shape[0], S_,
-                                     kv8, _stream(), None), "dmcp_reduce_rope_kv")
-    return q_out
+    return _rope_kv(_WMX, (xq, xs, wq, ws), pos, slot, cos_sin, k_cache, v_cache, n_q_heads, workspace,
+                    "wgemm_mx_rope_kv", q_out)
 
 
 # ---------------------------------------------------------------- tgemm
@@ -1306,17 +1222,8 @@ def tgemm_plan(M: int, N: int, K: int, mode: str = "part", cus: int = 256) -> tu
     return best[1], best[2]
 
 
-def _tgemm_args(x: torch.Tensor, w: torch.Tensor, name: str, swiglu: bool = False) -> tuple:
-    _req(x, torch.bfloat16, f"{name}.x")
-    _req(w, torch.bfloat16, f"{name}.w")
-    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
-        raise HipOpsError(f"{name}: x {tuple(x.shape)} / w {tuple(w.shape)} are not [M, K] / [N, K]")
-    M, K = x.shape
-    N = w.shape[0]
-    if not 1 <= M <= TGEMM_MAX_ROWS or not tgemm_supported(N, K, swiglu):
-        raise HipOpsError(f"{name}: needs 1 <= M <= {TGEMM_MAX_ROWS}, K % {TGEMM_KC} == 0, N % {TGEMM_NB} == 0 "
-                          f"(M={M} K={K} N={N})")
-    return M, K, N
+def _tgemm_args(x: torch.Tensor, w: torch.Tensor, name: str) -> tuple:
+    return _gemm_args(x, w, name, TGEMM_MAX_ROWS, TGEMM_NB)
 
 
 def _tg(x, w, y, part, M, N, K, S, mparts, mode, inter=0, masks=None, midx=None, n_masks=0, wwords=0, ids=None,
@@ -1340,7 +1247,7 @@ def tgemm_swiglu(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] =
                  mparts: int = 0) -> torch.Tensor:
     """silu(x . w[:I]^T) * (x . w[I:]^T) on the large-tile kernel (w = [gate; up],
     I % 128 == 0); returns [M, I]."""
-    M, K, N = _tgemm_args(x, w, "tgemm_swiglu", swiglu=True)
+    M, K, N = _tgemm_args(x, w, "tgemm_swiglu")
     inter = N // 2
     mparts = mparts or tgemm_plan(M, N, K, "swiglu")[1]
     if out is None:
@@ -1353,33 +1260,14 @@ def tgemm_swiglu(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] =
 def tgemm_partials(x: torch.Tensor, w: torch.Tensor, workspace: torch.Tensor, splits: int = 0,
                    mparts: int = 0) -> int:
     """fp32 split-K partials of x . w^T into ``workspace`` [S, M, N]; returns S."""
-    M, K, N = _tgemm_args(x, w, "tgemm_partials")
-    S, mp = tgemm_plan(M, N, K, "part")
-    S, mparts = splits or S, mparts or mp
-    chunks = K // TGEMM_KC
-    if S > chunks or (S - 1) * -(-chunks // S) >= chunks:
-        raise HipOpsError(f"tgemm_partials: K={K} does not split into {S} non-empty slices")
-    _wgemm_ws(workspace, S * M * N, "tgemm_partials")
-    _tg(x, w, None, workspace, M, N, K, S, mparts, 1, name="dmcp_tgemm[partials]")
-    return S
+    return _partials(_TGEMM, (x, w), workspace, "tgemm_partials", splits, mparts)
 
 
 def tgemm_resid_norm(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor, norm_w: torch.Tensor, eps: float,
                      workspace: torch.Tensor, out: Optional[torch.Tensor] = None, splits: int = 0) -> torch.Tensor:
     """residual += bf16(x . w^T) (in place); returns RMSNorm(residual) * norm_w
-    -- the large-tile split-K GEMM + wgemm.hip's fused reduction."""
-    M, K, N = _tgemm_args(x, w, "tgemm_resid_norm")
-    _req(residual, torch.bfloat16, "tgemm_resid_norm.residual")
-    _req(norm_w, torch.bfloat16, "tgemm_resid_norm.norm_w")
-    if tuple(residual.shape) != (M, N) or norm_w.numel() != N or N > 8192:
-        raise HipOpsError("tgemm_resid_norm: residual / norm weight shape mismatch")
-    S = tgemm_partials(x, w, workspace, splits)
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-    _req_out(out, torch.bfloat16, M * N, "tgemm_resid_norm.out")
-    _check(lib().dmcp_reduce_resid_norm(_ptr(workspace), S, _ptr(residual), _ptr(norm_w), _ptr(out), M, N,
-                                        float(eps), _stream()), "dmcp_reduce_resid_norm")
-    return out
+    -- the large-tile split-K GEMM + the fused reduction."""
+    return _resid_norm(_TGEMM, (x, w), residual, norm_w, eps, workspace, "tgemm_resid_norm", out, splits)
 
 
 def tgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
@@ -1388,25 +1276,8 @@ def tgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: tor
                   bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """rope_kv(F.linear(x, w, bias), ...) as the large-tile split-K GEMM + the
     fused bias / RoPE / q write / KV-append reduction; returns q [M, Hq, D]."""
-    M, K, N = _tgemm_args(x, w, "tgemm_rope_kv")
-    _req_bias(bias, N, "tgemm_rope_kv")
-    S_, Hkv, MAXS, D = k_cache.shape
-    kv8 = _req_kv(k_cache, v_cache, "tgemm_rope_kv")
-    _req(pos, torch.int32, "tgemm_rope_kv.pos")
-    _req(slot, torch.int32, "tgemm_rope_kv.slot")
-    _req(cos_sin, torch.float32, "tgemm_rope_kv.cos_sin")
-    if v_cache.shape != k_cache.shape or N != (n_q_heads + 2 * Hkv) * D or D % 16 or N > 8192:
-        raise HipOpsError(f"tgemm_rope_kv: w {tuple(w.shape)} does not match Hq={n_q_heads} / kv {tuple(k_cache.shape)}")
-    if pos.numel() != M or slot.numel() != M or cos_sin.dim() != 3 or tuple(cos_sin.shape[1:]) != (D // 2, 2):
-        raise HipOpsError("tgemm_rope_kv: pos/slot/cos_sin shape mismatch")
-    S = tgemm_partials(x, w, workspace, splits)
-    if q_out is None:
-        q_out = torch.empty((M, n_q_heads, D), dtype=torch.bfloat16, device=x.device)
-    _req_out(q_out, torch.bfloat16, M * n_q_heads * D, "tgemm_rope_kv.q_out")
-    _check(lib().dmcp_reduce_rope_kv(_ptr(workspace), S, _ptr(pos), _ptr(slot), _ptr(cos_sin), _ptr(q_out),
-                                     _ptr(k_cache), _ptr(v_cache), M, n_q_heads, Hkv, D, MAXS, cos_sin.shape[0], S_,
-                                     kv8, _stream(), _ptr(bias)), "dmcp_reduce_rope_kv")
-    return q_out
+    return _rope_kv(_TGEMM, (x, w), pos, slot, cos_sin, k_cache, v_cache, n_q_heads, workspace, "tgemm_rope_kv",
+                    q_out, splits, bias)
 
 
 def tgemm_lm_head_argmax(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_idx: torch.Tensor,
@@ -1432,3 +1303,132 @@ def tgemm_lm_head_argmax(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, 
     _tg(x, w, None, workspace, M, V, K, 1, mparts, 3, 0, masks, mask_idx, masks.shape[0], W, out,
         name="dmcp_tgemm[argmax]")
     return out
+
+
+# ---- split-K consumers (csrc/splitk_reduce.hip) -----------------------------
+# The three decode GEMM families write the same fp32 partials [S, M, N]; the
+# reductions that consume them are written once over a family's description.
+@dataclasses.dataclass(frozen=True)
+class _Family:
+    args: Callable    # (*operands, name) -> (M, K, N); raises on operands the kernel does not take
+    plan: Callable    # (M, N, K) -> (K slices S, M parts)
+    slices: Callable  # (K, S) -> whether S slices are valid for K
+    launch: Callable  # (operands, workspace, M, N, K, S, mparts): the partials GEMM
+
+
+def _slices_64(K: int, S: int) -> bool:
+    """wgemm / wmx: equal slices of whole 64-deep chunks."""
+    return S >= 1 and K % (64 * S) == 0
+
+
+def _slices_stages(K: int, S: int) -> bool:
+    """tgemm: ceil(stages / S) stages per slice, the last one shorter but not empty."""
+    chunks = K // TGEMM_KC
+    return 1 <= S <= chunks and (S - 1) * -(-chunks // S) < chunks
+
+
+def _wgemm_launch(ops, workspace, M, N, K, S, mparts) -> None:
+    x, w = ops
+    _check(lib().dmcp_wgemm(_ptr(x), _ptr(w), None, _ptr(workspace), M, N, K, S, mparts, 1, 0, _stream()),
+           "dmcp_wgemm[partials]")
+
+
+def _tgemm_launch(ops, workspace, M, N, K, S, mparts) -> None:
+    x, w = ops
+    _tg(x, w, None, workspace, M, N, K, S, mparts, 1, name="dmcp_tgemm[partials]")
+
+
+def _wmx_launch(ops, workspace, M, N, K, S, mparts) -> None:
+    xq, xs, wq, ws = ops
+    _check(lib().dmcp_wgemm_mx(_ptr(xq), _ptr(xs), _ptr(wq), _ptr(ws), _ptr(workspace), None, None, M, N, K, S,
+                               mparts, 1, 0, _stream()), "dmcp_wgemm_mx[partials]")
+
+
+_WGEMM = _Family(_wgemm_args, wgemm_plan, _slices_64, _wgemm_launch)
+_TGEMM = _Family(_tgemm_args, tgemm_plan, _slices_stages, _tgemm_launch)
+_WMX = _Family(_wmx_args, wmx_plan, _slices_64, _wmx_launch)
+
+
+def _plan_partials(fam: _Family, ops: tuple, workspace: torch.Tensor, name: str, splits: int = 0,
+                   mparts: int = 0) -> tuple:
+    """Checks the operands, the slicing and the workspace of a split-K GEMM;
+    returns what its launch takes: (M, N, K, S, mparts)."""
+    M, K, N = fam.args(*ops, name)
+    S, mp = fam.plan(M, N, K)
+    S, mparts = splits or S, mparts or mp
+    if not fam.slices(K, S):
+        raise HipOpsError(f"{name}: K={K} does not split into {S} slices")
+    _wgemm_ws(workspace, S * M * N, name)
+    return M, N, K, S, mparts
+
+
+def _partials(fam: _Family, ops: tuple, workspace: torch.Tensor, name: str, splits: int = 0, mparts: int = 0) -> int:
+    dims = _plan_partials(fam, ops, workspace, name, splits, mparts)
+    fam.launch(ops, workspace, *dims)
+    return dims[3]
+
+
+def _resid_norm(fam: _Family, ops: tuple, residual: torch.Tensor, norm_w: torch.Tensor, eps: float,
+                workspace: torch.Tensor, name: str, out, splits: int = 0, mx: bool = False):
+    """The partials GEMM, then the reduction that adds the residual and
+    normalises: bf16 ``out``, or (``mx``, N % 2048 == 0) an MXFP8 (q, s) pair."""
+    M, N, K, S, mparts = dims = _plan_partials(fam, ops, workspace, name, splits)
+    _req(residual, torch.bfloat16, f"{name}.residual")
+    _req(norm_w, torch.bfloat16, f"{name}.norm_w")
+    if tuple(residual.shape) != (M, N) or norm_w.numel() != N or N > 8192 or (mx and N % 2048):
+        raise HipOpsError(f"{name}: residual / norm weight shape mismatch (N <= 8192" +
+                          (", N % 2048 == 0)" if mx else ")"))
+    dev = residual.device
+    if mx:
+        q, s = out if out is not None else (torch.empty((M, N), dtype=torch.uint8, device=dev),
+                                            torch.empty((M, N // 32), dtype=torch.uint8, device=dev))
+        _req_out(q, torch.uint8, M * N, f"{name}.q")
+        _req_out(s, torch.uint8, M * N // 32, f"{name}.s")
+    else:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=dev) if out is None else out
+        _req_out(out, torch.bfloat16, M * N, f"{name}.out")
+    fam.launch(ops, workspace, *dims)
+    if mx:
+        _check(lib().dmcp_reduce_resid_norm_mx(_ptr(workspace), S, _ptr(residual), _ptr(norm_w), _ptr(q), _ptr(s), M,
+                                               N, float(eps), _stream()), "dmcp_reduce_resid_norm_mx")
+        return q, s
+    _check(lib().dmcp_reduce_resid_norm(_ptr(workspace), S, _ptr(residual), _ptr(norm_w), _ptr(out), M, N,
+                                        float(eps), _stream()), "dmcp_reduce_resid_norm")
+    return out
+
+
+def _rope_kv_args(name: str, M: int, N: int, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
+                  k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int,
+                  q_out: Optional[torch.Tensor]) -> tuple:
+    """pos / slot / cos_sin / caches / q_out of a QKV projection of M rows and
+    N columns; returns (q_out, kv8)."""
+    Hkv, D = k_cache.shape[1], k_cache.shape[3]
+    kv8 = _req_kv(k_cache, v_cache, name)
+    _req(pos, torch.int32, f"{name}.pos")
+    _req(slot, torch.int32, f"{name}.slot")
+    _req(cos_sin, torch.float32, f"{name}.cos_sin")
+    if N != (n_q_heads + 2 * Hkv) * D or D % 16 or N > 8192:
+        raise HipOpsError(f"{name}: {N} projection columns do not match Hq={n_q_heads} / kv {tuple(k_cache.shape)}")
+    if pos.numel() != M or slot.numel() != M or cos_sin.dim() != 3 or tuple(cos_sin.shape[1:]) != (D // 2, 2) \
+            or cos_sin.shape[0] < 1:
+        raise HipOpsError(f"{name}: pos/slot/cos_sin shape mismatch")
+    if q_out is None:
+        q_out = torch.empty((M, n_q_heads, D), dtype=torch.bfloat16, device=pos.device)
+    _req_out(q_out, torch.bfloat16, M * n_q_heads * D, f"{name}.q_out")
+    return q_out, kv8
+
+
+def _rope_kv(fam: _Family, ops: tuple, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
+             k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, workspace: torch.Tensor, name: str,
+             q_out: Optional[torch.Tensor] = None, splits: int = 0, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The partials GEMM of the QKV projection, then the reduction that adds
+    the bias, rotates q / k, writes q and appends k / v to the caches."""
+    M, N, K, S, mparts = dims = _plan_partials(fam, ops, workspace, name, splits)
+    _req_bias(bias, N, name)
+    q_out, kv8 = _rope_kv_args(name, M, N, pos, slot, cos_sin, k_cache, v_cache, n_q_heads, q_out)
+    slots, Hkv, max_seq, D = k_cache.shape
+    fam.launch(ops, workspace, *dims)
+    _check(lib().dmcp_reduce_rope_kv(_ptr(workspace), S, _ptr(pos), _ptr(slot), _ptr(cos_sin), _ptr(q_out),
+                                     _ptr(k_cache), _ptr(v_cache), M, n_q_heads, Hkv, D, max_seq, cos_sin.shape[0],
+                                     slots, kv8, _stream(), _ptr(bias)), "dmcp_reduce_rope_kv")
+    return q_out

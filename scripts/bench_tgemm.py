@@ -65,7 +65,7 @@ def main() -> int:
     # 1 / 2: no refill DMA / no compute; 16-18: 64-B image rows; 32 / 34: a 2-stage ring;
     # 64-66: the register-weight kernel (full / no refill / no compute), 129 / 130: its weights 1 / 2 stages ahead;
     # 256: the plain kernel, 257-262: + weight L2 prefetch 1-6 stages ahead
-    ap.add_argument("--probes", type=int, nargs="+", default=[1, 2, 16, 17, 18, 32, 34])
+    ap.add_argument("--probes", type=int, nargs="+", choices=[1, 2], default=[1, 2])
     ap.add_argument("--probe", action="store_true", help="also time the partials kernel without refill DMAs "
                     "(probe 1) and without compute (probe 2)")
     ap.add_argument("--probe-all", action="store_true", help="probes for gate/up and the head too (as plain "
