@@ -469,7 +469,7 @@ def create_backend(cfg) -> EnrichmentBackend:
             why = check_checkpoint(path)
             if why is not None:
                 reason = (f"ENRICH_BACKEND=local cannot load the checkpoint LOCAL_LLM_MODEL_PATH={path}: {why}. "
-                          f"Supported: Llama and Qwen2 checkpoints (docs/PARITY.md)")
+                          f"Supported: Llama, Qwen2 and Qwen3 checkpoints (docs/PARITY.md)")
                 LOG.error("%s", reason)
                 return RefusedBackend(reason)
 

@@ -40,8 +40,9 @@ MI355X mapping:
   (:class:`DecodeGraphs`), removing ~10 launches/layer of host overhead.
 
 Weights are random-initialised by default (no checkpoint on this host) or
-loaded from a Llama- or Qwen2-format safetensors directory
-(``load_safetensors``: RoPE scaling and q/k/v biases included; a directory
+loaded from a Llama-, Qwen2- or Qwen3-format safetensors directory
+(``load_safetensors``: RoPE scaling, q/k/v biases and Qwen3's per-head q/k
+RMSNorm included; a directory
 it cannot reproduce is refused, ``check_checkpoint``).
 """
 from __future__ import annotations
@@ -191,12 +192,16 @@ class CheckpointUnsupported(ValueError):
     (:func:`check_checkpoint` gives the reason)."""
 
 
-SUPPORTED_MODEL_TYPES = ("llama", "qwen2")
-SUPPORTED_ARCHITECTURES = ("LlamaForCausalLM", "Qwen2ForCausalLM")
+SUPPORTED_MODEL_TYPES = ("llama", "qwen2", "qwen3")
+SUPPORTED_ARCHITECTURES = ("LlamaForCausalLM", "Qwen2ForCausalLM", "Qwen3ForCausalLM")
 _LAYER_TENSORS = ("input_layernorm.weight", "post_attention_layernorm.weight", "self_attn.q_proj.weight",
                   "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.o_proj.weight",
                   "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
 _QKV_BIASES = ("self_attn.q_proj.bias", "self_attn.k_proj.bias", "self_attn.v_proj.bias")
+# Qwen3: RMSNorm over each q head and each k head (weight [head_dim]) between
+# the projection and RoPE
+_QK_NORMS = ("self_attn.q_norm.weight", "self_attn.k_norm.weight")
+QK_NORM_HEAD_DIMS = (64, 128)  # what the QK-norm kernels (and the attention kernels) take
 
 
 def _checkpoint_rope(hf: dict) -> Tuple[float, Optional[tuple]]:
@@ -218,6 +223,19 @@ def _checkpoint_tensor_names(path: str) -> List[str]:
             with safe_open(os.path.join(path, fn), framework="pt") as f:
                 names.extend(f.keys())
     return names
+
+
+def _checkpoint_tensor_shapes(path: str, suffixes: tuple) -> Dict[str, tuple]:
+    """Shapes of the tensors whose names end in ``suffixes`` (headers only)."""
+    from safetensors import safe_open
+    shapes: Dict[str, tuple] = {}
+    for fn in sorted(os.listdir(path)):
+        if fn.endswith(".safetensors"):
+            with safe_open(os.path.join(path, fn), framework="pt") as f:
+                for k in f.keys():
+                    if k.endswith(suffixes):
+                        shapes[k] = tuple(f.get_slice(k).get_shape())
+    return shapes
 
 
 def check_checkpoint(path: str) -> Optional[str]:
@@ -248,10 +266,18 @@ def check_checkpoint(path: str) -> Optional[str]:
         return "mlp_bias true is not supported (the MLP projections take no bias)"
     if hf.get("use_sliding_window"):
         return "use_sliding_window true is not supported (the attention kernels attend to every cached key)"
+    other = sorted({str(t) for t in hf.get("layer_types") or [] if t != "full_attention"})
+    if other:
+        return (f"layer_types contains {', '.join(other)} (only full_attention is supported: the attention "
+                f"kernels attend to every cached key)")
     heads = hf["num_attention_heads"]
     kvh = hf.get("num_key_value_heads", heads)
     if not isinstance(kvh, int) or kvh <= 0 or heads % kvh:
         return f"num_attention_heads {heads} is not a multiple of num_key_value_heads {kvh}"
+    qk_norm = mt == "qwen3"
+    head_dim = hf.get("head_dim") or hf["hidden_size"] // heads
+    if qk_norm and head_dim not in QK_NORM_HEAD_DIMS:
+        return f"head_dim {head_dim} is not supported with q_norm / k_norm (supported: 64, 128)"
     try:
         _checkpoint_rope(hf)
     except (ValueError, TypeError) as e:
@@ -269,6 +295,8 @@ def check_checkpoint(path: str) -> Optional[str]:
         p = f"model.layers.{i}."
         required.update(p + n for n in _LAYER_TENSORS)
         consumed.update(p + n for n in _QKV_BIASES)
+        if qk_norm:
+            required.update(p + n for n in _QK_NORMS)
     consumed |= required
     have = set(names)
     for n in names:  # the first tensor the loader would drop
@@ -276,7 +304,7 @@ def check_checkpoint(path: str) -> Optional[str]:
             continue
         if n.endswith((".o_proj.bias", ".gate_proj.bias", ".up_proj.bias", ".down_proj.bias")):
             return f"tensor {n} is not supported (only the q/k/v projections take a bias)"
-        return f"tensor {n} is not consumed by the loader (a layout other than Llama / Qwen2)"
+        return f"tensor {n} is not consumed by the loader (a layout other than Llama / Qwen2 / Qwen3)"
     missing = sorted(required - have)
     if missing:
         return f"tensor {missing[0]} is missing"
@@ -287,6 +315,14 @@ def check_checkpoint(path: str) -> Optional[str]:
             return f"layer {i} has {nb} of the 3 q/k/v bias tensors ({p}self_attn.*_proj.bias)"
         if hf.get("attention_bias") is False and nb:
             return f"attention_bias is false but {p}self_attn.q_proj.bias exists"
+    if qk_norm:
+        try:
+            shapes = _checkpoint_tensor_shapes(path, _QK_NORMS)
+        except Exception as e:  # noqa: BLE001
+            return f"safetensors of {path} cannot be read ({e})"
+        for n in sorted(shapes):
+            if shapes[n] != (head_dim,):
+                return f"tensor {n} has shape {list(shapes[n])}, expected [{head_dim}] (head_dim)"
     if "lm_head.weight" not in have and hf.get("tie_word_embeddings") is False:
         return "tensor lm_head.weight is missing and tie_word_embeddings is false"
     return None
@@ -380,6 +416,15 @@ class LocalLM:
                              f"use prefill_dtype / decode_dtype 'bf16' (LOCAL_LLM_PREFILL_DTYPE, "
                              f"LOCAL_LLM_DECODE_DTYPE), got prefill_dtype={cfg.prefill_dtype!r} "
                              f"decode_dtype={cfg.decode_dtype!r}")
+        # per-head q / k RMSNorm (Qwen3 checkpoints): w["l{i}.qnorm"] / w["l{i}.knorm"], bf16 [head_dim]
+        self.has_qk_norm = any(k.endswith(".qnorm") for k in self.w)
+        if self.has_qk_norm and "fp8" in (cfg.prefill_dtype, cfg.decode_dtype):
+            raise ValueError(f"{cfg.name} has per-head q/k norms, which the MXFP8 GEMMs do not apply: "
+                             f"use prefill_dtype / decode_dtype 'bf16' (LOCAL_LLM_PREFILL_DTYPE, "
+                             f"LOCAL_LLM_DECODE_DTYPE), got prefill_dtype={cfg.prefill_dtype!r} "
+                             f"decode_dtype={cfg.decode_dtype!r}")
+        if self.has_qk_norm and cfg.head_dim not in QK_NORM_HEAD_DIMS:
+            raise ValueError(f"{cfg.name}: per-head q/k norms need head_dim 64 or 128, got {cfg.head_dim}")
         self._fold_norms()
         c = cfg
         self.shared_prefix = shared_prefix
@@ -392,8 +437,9 @@ class LocalLM:
         self._check_kv_fits(kv_shape)
         self.k_cache = torch.zeros(kv_shape, dtype=self.kv_dtype, device=self.device)
         self.v_cache = torch.zeros(kv_shape, dtype=self.kv_dtype, device=self.device)
+        # (a QK-norm model's table is built in fp32 like its own code's: ops.reference.rope_tables)
         self.cos_sin = ops.rope_tables(c.max_seq, c.head_dim, c.rope_theta, device=self.device,
-                                       scaling=c.rope_scaling).contiguous()
+                                       scaling=c.rope_scaling, fp32_angles=self.has_qk_norm).contiguous()
         self.scale = 1.0 / math.sqrt(c.head_dim)
         self.max_rows = max(c.max_batch, c.max_rows)
         # method branches: per slot (parent slot, end) -- the decode attention
@@ -412,7 +458,10 @@ class LocalLM:
         self.prefix_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
         # fused decode GEMMs for steps of <= fused_max_rows rows (GPU only;
         # the attribute is cleared by tests to compare against hipBLASLt)
-        self.use_fused = self.device.type == "cuda" and fused_shapes_ok(c)
+        # (a QK-norm model with q/k/v biases takes the weight-streaming path
+        # at every row count: the two-launch small-row QKV has no bias input)
+        self.use_fused = (self.device.type == "cuda" and fused_shapes_ok(c)
+                          and not (self.has_qk_norm and self.has_bias))
         # prefill / extend attention on the MFMA kernel (csrc/prefill_attn.hip)
         self.use_prefill_kernel = (self.device.type == "cuda"
                                    and ops.prefill_supported(c.n_heads, c.n_kv_heads, c.head_dim))
@@ -423,6 +472,11 @@ class LocalLM:
         # (fp8: fused 1.47 vs 1.64 ms at 16 rows, 1.80 vs 1.70 at 24, 1.82 vs
         # 1.73 at 32 -- profiles/decode_fused_rows_r2.txt)
         self.fused_max_rows = min(ops.FUSED_MAX_ROWS, 16)
+        # QK-norm models: the small-row step's bf16 QKV row (fused_linear_norm
+        # writes it, rope_kv normalises and rotates it), preallocated so a
+        # captured step allocates nothing for it
+        self.qkv_buf = (torch.empty((self.fused_max_rows, c.qkv_dim), dtype=self.dtype, device=self.device)
+                        if self.has_qk_norm and self.use_fused else None)
         ps = ops.PREFIX_MFMA_MAX_SPLITS if shared_prefix else 0
         self.attn_ws = (ops.decode_workspace(self.max_rows, c.n_heads, c.n_kv_heads, c.head_dim, c.max_seq,
                                              self.device, prefix_slots=ps) if self.device.type == "cuda" else None)
@@ -463,7 +517,7 @@ class LocalLM:
             or (self.device.type == "cpu" and c.hidden % 32 == 0 and c.intermediate % 32 == 0))
         self.prefill_fp8 = fp8_ok and (c.prefill_dtype == "fp8"
                                        or (c.prefill_dtype == "auto" and self.device.type == "cuda"
-                                           and not self.has_bias))
+                                           and not self.has_bias and not self.has_qk_norm))
         self.decode_fp8 = c.decode_dtype == "fp8" and fp8_ok
         if "fp8" in (c.prefill_dtype, c.decode_dtype) and not fp8_ok:
             raise ValueError(f"fp8 GEMMs need head_dim 64, hidden % 2048 == 0 and a supported device "
@@ -575,9 +629,10 @@ class LocalLM:
 
     @classmethod
     def load_safetensors(cls, path: str, device: str = "cuda", **cfg_overrides) -> "LocalLM":
-        """Loads a Llama- or Qwen2-format checkpoint directory (config.json +
-        *.safetensors) as the model it is: RoPE scaling ("linear", "llama3")
-        and q/k/v projection biases included.  A directory the loader cannot
+        """Loads a Llama-, Qwen2- or Qwen3-format checkpoint directory
+        (config.json + *.safetensors) as the model it is: RoPE scaling
+        ("linear", "llama3"), q/k/v projection biases and Qwen3's per-head
+        q/k RMSNorm included.  A directory the loader cannot
         reproduce raises :class:`CheckpointUnsupported` with the reason
         (:func:`check_checkpoint`)."""
         from safetensors.torch import load_file
@@ -620,6 +675,9 @@ class LocalLM:
             if p + "self_attn.q_proj.bias" in raw:  # Qwen2: q/k/v biases, stacked like wqkv
                 w[f"l{i}.bqkv"] = torch.cat([g(p + "self_attn.q_proj.bias"), g(p + "self_attn.k_proj.bias"),
                                              g(p + "self_attn.v_proj.bias")], 0).contiguous()
+            if hf.get("model_type") == "qwen3":  # per-head q / k RMSNorm weights [head_dim]
+                w[f"l{i}.qnorm"] = g(p + "self_attn.q_norm.weight")
+                w[f"l{i}.knorm"] = g(p + "self_attn.k_norm.weight")
             w[f"l{i}.wo"] = g(p + "self_attn.o_proj.weight")
             w[f"l{i}.wgu"] = torch.cat([g(p + "mlp.gate_proj.weight"), g(p + "mlp.up_proj.weight")], 0).contiguous()
             w[f"l{i}.wdown"] = g(p + "mlp.down_proj.weight")
@@ -628,6 +686,12 @@ class LocalLM:
         return m
 
     # ------------------------------------------------------------ forward
+    def _qk_norm(self, i: int) -> Optional[tuple]:
+        """Layer i's ``qk_norm`` argument of the QKV ops: (q weight, k weight, eps) or None."""
+        if not self.has_qk_norm:
+            return None
+        return self.w[f"l{i}.qnorm"], self.w[f"l{i}.knorm"], self.cfg.eps
+
     def _mlp(self, i: int, h: torch.Tensor) -> torch.Tensor:
         gu = F.linear(h, self.w[f"l{i}.wgu"])
         return F.linear(ops.silu_mul(gu), self.w[f"l{i}.wdown"])
@@ -659,7 +723,7 @@ class LocalLM:
         for i in range(c.layers):
             kc, vc = self.k_cache[i], self.v_cache[i]
             qkv = F.linear(h, self.w[f"l{i}.wqkv"], self.w.get(f"l{i}.bqkv"))
-            q = ops.rope_kv(qkv, pos, slots, self.cos_sin, kc, vc, c.n_heads)  # [T, Hq, D]
+            q = ops.rope_kv(qkv, pos, slots, self.cos_sin, kc, vc, c.n_heads, qk_norm=self._qk_norm(i))  # [T, Hq, D]
             if self.use_prefill_kernel:
                 att = ops.prefill_attention(q, kc, vc, slot, start_pos, self.prefix_slot if shared else None,
                                             shared, self.scale)
@@ -744,7 +808,8 @@ class LocalLM:
         for i in range(c.layers):
             kc, vc = self.k_cache[i], self.v_cache[i]
             qkv = F.linear(h, self.w[f"l{i}.wqkv"], self.w.get(f"l{i}.bqkv"))
-            q = ops.rope_kv(qkv, pos_t, slot_t, self.cos_sin, kc, vc, c.n_heads)  # [Ttot, Hq, D]
+            q = ops.rope_kv(qkv, pos_t, slot_t, self.cos_sin, kc, vc, c.n_heads,
+                            qk_norm=self._qk_norm(i))  # [Ttot, Hq, D]
             att = ops.prefill_attention_varlen(q, kc, vc, offsets, seq_slots, starts, prefix, shared, self.scale)
             o = F.linear(att.view(Ttot, c.n_heads * c.head_dim), self.w[f"l{i}.wo"])
             h = ops.add_rmsnorm(o, self.w[f"l{i}.ln2"], c.eps, residual=resid)
@@ -833,15 +898,16 @@ class LocalLM:
             kc, vc = self.k_cache[i], self.v_cache[i]
             nxt = self.w[f"l{i + 1}.ln1"] if i + 1 < c.layers else self.w["norm_f"]
             bqkv = self.w.get(f"l{i}.bqkv")
+            qkn = self._qk_norm(i)
             if big:
                 q = ops.tgemm_rope_kv(h, self.w[f"l{i}.wqkv"], positions, slots, self.cos_sin, kc, vc, c.n_heads,
-                                      self.tg_ws, bias=bqkv)
+                                      self.tg_ws, bias=bqkv, qk_norm=qkn)
             elif wide:
                 q = ops.wgemm_rope_kv(h, self.w[f"l{i}.wqkv"], positions, slots, self.cos_sin, kc, vc, c.n_heads,
-                                      self.wgemm_ws, bias=bqkv)
+                                      self.wgemm_ws, bias=bqkv, qk_norm=qkn)
             else:
                 q = ops.rope_kv(F.linear(h, self.w[f"l{i}.wqkv"], bqkv), positions, slots, self.cos_sin, kc, vc,
-                                c.n_heads)
+                                c.n_heads, qk_norm=qkn)
             att = ops.decode_attention(q, kc, vc, slots, seq_len, self.scale, workspace=self.attn_ws, chunk=chunk,
                                        fork=self.fork_tab,
                                        prefix=self._prefix(i, prefix_rows), splits=splits).view(B, c.n_heads * c.head_dim)
@@ -926,8 +992,16 @@ class LocalLM:
                                               mask_idx, mask_alt, alt_token)
         for i in range(c.layers):
             kc, vc = self.k_cache[i], self.v_cache[i]
-            q = ops.fused_rope_kv(r, self.w[f"l{i}.wqkv"], c.eps, positions, slots, self.cos_sin, kc, vc, c.n_heads,
-                                  bias=self.w.get(f"l{i}.bqkv"))
+            if self.has_qk_norm:
+                # the fused QKV tile holds 32 of a head's columns, so the
+                # per-head norm cannot sit in its epilogue: norm-folded QKV to
+                # a bf16 row, then the norm-taking RoPE + append (one launch
+                # more per layer; docs/KERNELS.md)
+                qkv = ops.fused_linear_norm(r, self.w[f"l{i}.wqkv"], c.eps, out=self.qkv_buf[:B])
+                q = ops.rope_kv(qkv, positions, slots, self.cos_sin, kc, vc, c.n_heads, qk_norm=self._qk_norm(i))
+            else:
+                q = ops.fused_rope_kv(r, self.w[f"l{i}.wqkv"], c.eps, positions, slots, self.cos_sin, kc, vc,
+                                      c.n_heads, bias=self.w.get(f"l{i}.bqkv"))
             att = ops.decode_attention(q, kc, vc, slots, seq_len, self.scale, workspace=self.attn_ws, chunk=chunk,
                                        fork=self.fork_tab,
                                        prefix=self._prefix(i, prefix_rows), splits=splits)
@@ -1115,8 +1189,12 @@ class LocalLM:
             if f"l{i}.bqkv" in w:
                 qkv = qkv + w[f"l{i}.bqkv"]
             qkv = qkv.view(T, c.n_heads + 2 * c.n_kv_heads, c.head_dim)
-            q = ops.reference.apply_rope(qkv[:, :c.n_heads], pos, cs)
-            k = ops.reference.apply_rope(qkv[:, c.n_heads:c.n_heads + c.n_kv_heads], pos, cs)
+            xq, xk = qkv[:, :c.n_heads], qkv[:, c.n_heads:c.n_heads + c.n_kv_heads]
+            if f"l{i}.qnorm" in w:
+                xq = ops.reference.head_rmsnorm(xq, w[f"l{i}.qnorm"], c.eps)
+                xk = ops.reference.head_rmsnorm(xk, w[f"l{i}.knorm"], c.eps)
+            q = ops.reference.apply_rope(xq, pos, cs)
+            k = ops.reference.apply_rope(xk, pos, cs)
             v = qkv[:, c.n_heads + c.n_kv_heads:]
             k = k.repeat_interleave(G, dim=1)
             v = v.repeat_interleave(G, dim=1)

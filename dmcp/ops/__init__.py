@@ -47,7 +47,7 @@ def _by_device(name: str):
 # ops with an fp32 CPU reference: norms, RoPE + KV append, prefill attention,
 # SwiGLU, selection, embedding, the decode step's input gather + first norm,
 # the MXFP8 prefill path (csrc/pgemm.hip), and the three fused QKV projections
-# (their references define where the optional bias enters)
+# (their references define where the optional bias and QK-norm enter)
 DEVICE_OPS = ("add_rmsnorm", "rope_kv", "prefill_attention", "prefill_attention_varlen", "silu_mul",
               "masked_argmax", "lm_head_argmax", "embedding", "decode_embed_norm", "mx_quant", "rmsnorm_mx",
               "pgemm", "pgemm_resid", "pgemm_swiglu", "pgemm_qkv", "fused_rope_kv", "wgemm_rope_kv", "tgemm_rope_kv")

@@ -65,6 +65,30 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// Per-head RMSNorm of a q or k head in the RoPE thread mapping: a lane holds
+// dims [d0, d0 + 4) of a head in x1 and their rotary partners (+ D/2) in x2,
+// so a head is D/8 consecutive lanes (8 at D = 64, 16 at D = 128), aligned to
+// their count and inside one wave.  Every lane of a head must be active.
+// x <- x * rsqrt(mean_d(x^2) + eps) * w[d], all fp32; w is bf16 [D].
+__device__ __forceinline__ void qk_norm_quad(float* x1, float* x2, const uint16_t* __restrict__ w, int d0, int D,
+                                             float eps) {
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ss += x1[j] * x1[j] + x2[j] * x2[j];
+#pragma unroll
+    for (int m = 1; m < 8; m <<= 1) ss += __shfl_xor(ss, m, kWave);
+    if (D == 128) ss += __shfl_xor(ss, 8, kWave);  // D is uniform: no divergence at the shuffle
+    const float inv = rsqrtf(ss / (float)D + eps);
+    float w1[4], w2[4];
+    unpack4(*reinterpret_cast<const uint2*>(w + d0), w1);
+    unpack4(*reinterpret_cast<const uint2*>(w + (D >> 1) + d0), w2);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        x1[j] = x1[j] * inv * w1[j];
+        x2[j] = x2[j] * inv * w2[j];
+    }
+}
+
 __device__ __forceinline__ float silu(float g) { return g / (1.f + __expf(-g)); }
 
 // LDS-DMA (global_load_lds_dwordx4): each lane's 16 source bytes land at

@@ -115,8 +115,10 @@ __global__ __launch_bounds__(kBlock) void add_rmsnorm_kernel(const uint16_t* __r
 //    k/v cache [S, Hkv, MAXS, D] written at (slot[t], :, pos[t], :)
 //    cos_sin [max_pos, D/2] float2 (cos, sin)
 //    KV8: the caches hold fp8 e4m3 (saturated), q stays bf16
+//    QKN: per-head RMSNorm of q (weight qn [D]) and k (kn [D]) in fp32 ahead
+//         of the rotation (qk_norm_quad, dmcp_common.hpp); D is 64 or 128
 // --------------------------------------------------------------------------
-template <bool KV8>
+template <bool KV8, bool QKN = false>
 __global__ __launch_bounds__(kBlock) void rope_kv_kernel(const uint16_t* __restrict__ qkv,
                                                         const int32_t* __restrict__ pos,
                                                         const int32_t* __restrict__ slot,
@@ -124,7 +126,10 @@ __global__ __launch_bounds__(kBlock) void rope_kv_kernel(const uint16_t* __restr
                                                         uint16_t* __restrict__ q_out,
                                                         void* __restrict__ k_cache,
                                                         void* __restrict__ v_cache, int Hq, int Hkv,
-                                                        int D, int max_seq, int max_pos, int num_slots) {
+                                                        int D, int max_seq, int max_pos, int num_slots,
+                                                        const uint16_t* __restrict__ qn = nullptr,
+                                                        const uint16_t* __restrict__ kn = nullptr,
+                                                        float eps = 0.f) {
     const int t = blockIdx.x;
     const int p = pos[t];
     const int s = slot[t];
@@ -141,6 +146,7 @@ __global__ __launch_bounds__(kBlock) void rope_kv_kernel(const uint16_t* __restr
         float x1[4], x2[4], o1[4], o2[4];
         unpack4(*reinterpret_cast<const uint2*>(src + d0), x1);
         unpack4(*reinterpret_cast<const uint2*>(src + half + d0), x2);
+        if constexpr (QKN) qk_norm_quad(x1, x2, hh < Hq ? qn : kn, d0, D, eps);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float2 c = cs[d0 + j];
@@ -956,7 +962,7 @@ __global__ __launch_bounds__(kBlock) void kv_fork_kernel(uint8_t* __restrict__ k
 
 extern "C" {
 
-int dmcp_abi_version() { return 19; }
+int dmcp_abi_version() { return 20; }
 
 int dmcp_add_rmsnorm(const void* x, void* residual, const void* w, void* out, int rows, int H, float eps,
                      void* stream) {
@@ -987,6 +993,27 @@ int dmcp_rope_kv(const void* qkv, const void* pos, const void* slot, const void*
         rope_kv_kernel<false><<<T, kBlock, 0, st>>>((const uint16_t*)qkv, (const int32_t*)pos, (const int32_t*)slot,
                                                     (const float2*)cos_sin, (uint16_t*)q_out, k_cache, v_cache, Hq,
                                                     Hkv, D, max_seq, max_pos, num_slots);
+    return hipGetLastError();
+}
+
+// dmcp_rope_kv with the per-head q / k RMSNorm (weights qn / kn [D] bf16)
+// ahead of the rotation; D is 64 or 128
+int dmcp_rope_kv_norm(const void* qkv, const void* pos, const void* slot, const void* cos_sin, void* q_out,
+                      void* k_cache, void* v_cache, int T, int Hq, int Hkv, int D, int max_seq, int max_pos,
+                      int num_slots, int kv8, void* stream, const void* qn, const void* kn, float eps) {
+    if (T <= 0) return 0;
+    if ((D != 64 && D != 128) || !qn || !kn) return hipErrorInvalidValue;
+    auto st = (hipStream_t)stream;
+    if (kv8)
+        rope_kv_kernel<true, true><<<T, kBlock, 0, st>>>(
+            (const uint16_t*)qkv, (const int32_t*)pos, (const int32_t*)slot, (const float2*)cos_sin,
+            (uint16_t*)q_out, k_cache, v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots, (const uint16_t*)qn,
+            (const uint16_t*)kn, eps);
+    else
+        rope_kv_kernel<false, true><<<T, kBlock, 0, st>>>(
+            (const uint16_t*)qkv, (const int32_t*)pos, (const int32_t*)slot, (const float2*)cos_sin,
+            (uint16_t*)q_out, k_cache, v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots, (const uint16_t*)qn,
+            (const uint16_t*)kn, eps);
     return hipGetLastError();
 }
 

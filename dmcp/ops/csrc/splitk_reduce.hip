@@ -107,13 +107,15 @@ __global__ __launch_bounds__(kBlock) void reduce_resid_norm_kernel(const float* 
 // split-K reduction of the QKV projection + rotate-half RoPE on q and k, q
 // written out, k / v appended to the KV cache (bf16, or KV8 fp8 e4m3) at
 // (slot[t], :, pos[t], :) -- dmcp_kernels.hip::rope_kv_kernel over an LDS row
-// of the bf16-rounded sum (what F.linear + rope_kv compute).
-template <bool KV8>
+// of the bf16-rounded sum (what F.linear + rope_kv compute).  QKN: the
+// per-head q / k RMSNorm (qk_norm_quad) on the bf16 row ahead of the rotation.
+template <bool KV8, bool QKN = false>
 __global__ __launch_bounds__(kBlock) void reduce_rope_kv_kernel(
     const float* __restrict__ part, int S, int M, const int32_t* __restrict__ pos, const int32_t* __restrict__ slot,
     const float2* __restrict__ cos_sin, uint16_t* __restrict__ q_out, void* __restrict__ k_cache,
     void* __restrict__ v_cache, int Hq, int Hkv, int D, int max_seq, int max_pos, int num_slots,
-    const uint16_t* __restrict__ bias) {
+    const uint16_t* __restrict__ bias, const uint16_t* __restrict__ qn = nullptr,
+    const uint16_t* __restrict__ kn = nullptr, float eps = 0.f) {
     __shared__ uint4 rowbuf[8192 / 8];
     const int t = blockIdx.x;
     const int N = (Hq + 2 * Hkv) * D;
@@ -145,6 +147,7 @@ __global__ __launch_bounds__(kBlock) void reduce_rope_kv_kernel(
         float x1[4], x2[4], o1[4], o2[4];
         unpack4(*reinterpret_cast<const uint2*>(src + d0), x1);
         unpack4(*reinterpret_cast<const uint2*>(src + half + d0), x2);
+        if constexpr (QKN) qk_norm_quad(x1, x2, hh < Hq ? qn : kn, d0, D, eps);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float2 c = cs[d0 + j];
@@ -284,6 +287,30 @@ int dmcp_reduce_rope_kv(const void* part, int S, const void* pos, const void* sl
         reduce_rope_kv_kernel<false><<<M, kBlock, 0, st>>>(pp, S, M, (const int32_t*)pos, (const int32_t*)slot,
                                                            (const float2*)cos_sin, (uint16_t*)q_out, k_cache,
                                                            v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots, bb);
+    return hipGetLastError();
+}
+
+// dmcp_reduce_rope_kv with the per-head q / k RMSNorm (weights qn / kn [D]
+// bf16) between the bias and the rotation; D is 64 or 128
+int dmcp_reduce_rope_kv_norm(const void* part, int S, const void* pos, const void* slot, const void* cos_sin,
+                             void* q_out, void* k_cache, void* v_cache, int M, int Hq, int Hkv, int D, int max_seq,
+                             int max_pos, int num_slots, int kv8, void* stream, const void* bias, const void* qn,
+                             const void* kn, float eps) {
+    if (M <= 0) return 0;
+    if (!part || S < 1 || (D != 64 && D != 128) || (Hq + 2 * Hkv) * D > 8192 || !pos || !slot || !cos_sin ||
+        !q_out || !k_cache || !v_cache || max_pos <= 0 || !qn || !kn)
+        return hipErrorInvalidValue;
+    auto st = (hipStream_t)stream;
+    auto pp = (const float*)part;
+    auto bb = (const uint16_t*)bias;  // [N] bf16 or nullptr
+    if (kv8)
+        reduce_rope_kv_kernel<true, true><<<M, kBlock, 0, st>>>(
+            pp, S, M, (const int32_t*)pos, (const int32_t*)slot, (const float2*)cos_sin, (uint16_t*)q_out, k_cache,
+            v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots, bb, (const uint16_t*)qn, (const uint16_t*)kn, eps);
+    else
+        reduce_rope_kv_kernel<false, true><<<M, kBlock, 0, st>>>(
+            pp, S, M, (const int32_t*)pos, (const int32_t*)slot, (const float2*)cos_sin, (uint16_t*)q_out, k_cache,
+            v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots, bb, (const uint16_t*)qn, (const uint16_t*)kn, eps);
     return hipGetLastError();
 }
 

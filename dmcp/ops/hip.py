@@ -28,7 +28,7 @@ _lock = threading.Lock()
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
-ABI_VERSION = 19  # must match dmcp_abi_version() in csrc/dmcp_kernels.hip
+ABI_VERSION = 20  # must match dmcp_abi_version() in csrc/dmcp_kernels.hip
 
 
 class HipOpsError(RuntimeError):
@@ -55,6 +55,8 @@ def lib() -> ctypes.CDLL:
             "dmcp_lm_head_argmax": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp], _i),
             "dmcp_add_rmsnorm": ([_vp, _vp, _vp, _vp, _i, _i, _f, _vp], _i),
             "dmcp_rope_kv": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
+            "dmcp_rope_kv_norm": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f],
+                                  _i),
             "dmcp_decode_attention": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f,
                                        _vp, _vp, _vp, _i, _i, _vp, _vp, _vp], _i),
             "dmcp_kv_fork": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp], _i),
@@ -85,6 +87,8 @@ def lib() -> ctypes.CDLL:
             "dmcp_reduce_resid_norm": ([_vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp], _i),
             "dmcp_reduce_rope_kv": ([_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp],
                                     _i),
+            "dmcp_reduce_rope_kv_norm": ([_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp,
+                                          _vp, _vp, _vp, _f], _i),
             "dmcp_wgemm": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
             "dmcp_tgemm": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp], _i),
             "dmcp_tgemm_probe": ([_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
@@ -160,6 +164,28 @@ def _req_bias(bias: Optional[torch.Tensor], n: int, name: str) -> None:
         raise HipOpsError(f"{name}: bias holds {bias.numel()} elements, the projection has {n} columns")
 
 
+QK_NORM_DIMS = (64, 128)  # head sizes whose RoPE lane groups (D / 8 lanes a head) the QK-norm kernels reduce over
+
+
+def _req_qk_norm(qk_norm: Optional[tuple], D: int, name: str) -> Optional[tuple]:
+    """An optional per-head q / k RMSNorm ``(q_weight, k_weight, eps)``: bf16
+    weights of one head's D values each; returns it with eps as a float."""
+    if qk_norm is None:
+        return None
+    if not isinstance(qk_norm, (tuple, list)) or len(qk_norm) != 3:
+        raise HipOpsError(f"{name}: qk_norm must be (q_weight, k_weight, eps)")
+    qw, kw, eps = qk_norm
+    if D not in QK_NORM_DIMS:
+        raise HipOpsError(f"{name}: qk_norm needs head_dim in {QK_NORM_DIMS}, got {D}")
+    for t, which in ((qw, "q_weight"), (kw, "k_weight")):
+        if not isinstance(t, torch.Tensor):
+            raise HipOpsError(f"{name}.qk_norm.{which}: expected a tensor")
+        _req(t, torch.bfloat16, f"{name}.qk_norm.{which}")
+        if t.numel() != D:
+            raise HipOpsError(f"{name}.qk_norm.{which}: holds {t.numel()} elements, a head has {D}")
+    return qw, kw, float(eps)
+
+
 # ---------------------------------------------------------------- wrappers
 def add_rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float, residual: Optional[torch.Tensor] = None,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -183,9 +209,11 @@ def add_rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float, residual: Opt
 
 
 def rope_kv(qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
-            k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, q_out: Optional[torch.Tensor] = None
-            ) -> torch.Tensor:
-    """k_cache/v_cache: [S, Hkv, MAXS, D]; returns q [T, Hq, D]."""
+            k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, q_out: Optional[torch.Tensor] = None,
+            qk_norm: Optional[tuple] = None) -> torch.Tensor:
+    """k_cache/v_cache: [S, Hkv, MAXS, D]; returns q [T, Hq, D].  ``qk_norm``
+    (q_weight [D], k_weight [D], eps): per-head RMSNorm of q and k in fp32
+    ahead of the rotation (D 64 or 128)."""
     S, Hkv, MAXS, D = k_cache.shape
     T = qkv.shape[0]
     _req(qkv, torch.bfloat16, "rope_kv.qkv")
@@ -203,6 +231,13 @@ def rope_kv(qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: t
     if q_out is None:
         q_out = torch.empty((T, n_q_heads, D), dtype=torch.bfloat16, device=qkv.device)
     _req_out(q_out, torch.bfloat16, T * n_q_heads * D, "rope_kv.q_out")
+    qk_norm = _req_qk_norm(qk_norm, D, "rope_kv")
+    if qk_norm is not None:
+        qw, kw, neps = qk_norm
+        _check(lib().dmcp_rope_kv_norm(_ptr(qkv), _ptr(pos), _ptr(slot), _ptr(cos_sin), _ptr(q_out), _ptr(k_cache),
+                                       _ptr(v_cache), T, n_q_heads, Hkv, D, MAXS, max_pos, S, kv8, _stream(),
+                                       _ptr(qw), _ptr(kw), neps), "dmcp_rope_kv_norm")
+        return q_out
     _check(lib().dmcp_rope_kv(_ptr(qkv), _ptr(pos), _ptr(slot), _ptr(cos_sin), _ptr(q_out), _ptr(k_cache),
                               _ptr(v_cache), T, n_q_heads, Hkv, D, MAXS, max_pos, S, kv8, _stream()), "dmcp_rope_kv")
     return q_out
@@ -702,11 +737,16 @@ def _fused(epi: str, wk: int, x, w, out, M, K, N, eps=0.0, inter=0, pos=None, sl
 def fused_rope_kv(x: torch.Tensor, w: torch.Tensor, eps: float, pos: torch.Tensor, slot: torch.Tensor,
                   cos_sin: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int,
                   q_out: Optional[torch.Tensor] = None, wk: int = 8,
-                  bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None) -> torch.Tensor:
     """q = RoPE(rms(x) . w[:Hq*D]^T); RoPE(k) and v appended to the KV cache at
     (slot[m], :, pos[m]) -- the RMSNorm weight must be folded into ``w``.
     x [M, K]; w [(Hq + 2 Hkv) D, K]; caches [S, Hkv, MAXS, D]; ``bias`` [N]
-    bf16 is added to the normalised fp32 product before RoPE.  Returns q [M, Hq, D]."""
+    bf16 is added to the normalised fp32 product before RoPE.  Returns q [M, Hq, D].
+    ``qk_norm`` is the CPU reference's only: this kernel's tile holds 32 of a
+    head's columns, so a QK-norm model runs fused_linear_norm + rope_kv."""
+    if qk_norm is not None:
+        raise HipOpsError("fused_rope_kv: the kernel takes no qk_norm (a block holds 32 of a head's columns); "
+                          "use fused_linear_norm followed by rope_kv(qk_norm=...)")
     M, K, N = _fused_xw(x, w, "fused_rope_kv")
     _req_bias(bias, N, "fused_rope_kv")
     S, Hkv, MAXS, D = k_cache.shape
@@ -919,12 +959,14 @@ def wgemm_resid_norm(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor, n
 def wgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
                   k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, workspace: torch.Tensor,
                   q_out: Optional[torch.Tensor] = None, splits: int = 0,
-                  bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None) -> torch.Tensor:
     """rope_kv(F.linear(x, w, bias), ...) as one split-K GEMM + one reduction per
     row (the bias on the fp32 sum, RoPE, the q write and the K/V-cache append).
-    x [M, K] (M <= WGEMM_MAX_ROWS); returns q [M, Hq, D]."""
+    x [M, K] (M <= WGEMM_MAX_ROWS); returns q [M, Hq, D].  ``qk_norm``
+    (q_weight [D], k_weight [D], eps): per-head RMSNorm of q and k between the
+    bias and the rotation, in the same reduction."""
     return _rope_kv(_WGEMM, (x, w), pos, slot, cos_sin, k_cache, v_cache, n_q_heads, workspace, "wgemm_rope_kv",
-                    q_out, splits, bias)
+                    q_out, splits, bias, qk_norm)
 
 
 def wgemm_workspace(rows: int, n_max: int, device) -> torch.Tensor:
@@ -1273,11 +1315,11 @@ def tgemm_resid_norm(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor, n
 def tgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
                   k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, workspace: torch.Tensor,
                   q_out: Optional[torch.Tensor] = None, splits: int = 0,
-                  bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None) -> torch.Tensor:
     """rope_kv(F.linear(x, w, bias), ...) as the large-tile split-K GEMM + the
     fused bias / RoPE / q write / KV-append reduction; returns q [M, Hq, D]."""
     return _rope_kv(_TGEMM, (x, w), pos, slot, cos_sin, k_cache, v_cache, n_q_heads, workspace, "tgemm_rope_kv",
-                    q_out, splits, bias)
+                    q_out, splits, bias, qk_norm)
 
 
 def tgemm_lm_head_argmax(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_idx: torch.Tensor,
@@ -1420,14 +1462,24 @@ def _rope_kv_args(name: str, M: int, N: int, pos: torch.Tensor, slot: torch.Tens
 
 def _rope_kv(fam: _Family, ops: tuple, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
              k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, workspace: torch.Tensor, name: str,
-             q_out: Optional[torch.Tensor] = None, splits: int = 0, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+             q_out: Optional[torch.Tensor] = None, splits: int = 0, bias: Optional[torch.Tensor] = None,
+             qk_norm: Optional[tuple] = None) -> torch.Tensor:
     """The partials GEMM of the QKV projection, then the reduction that adds
-    the bias, rotates q / k, writes q and appends k / v to the caches."""
+    the bias, (``qk_norm``) normalises the q / k heads, rotates them, writes q
+    and appends k / v to the caches."""
     M, N, K, S, mparts = dims = _plan_partials(fam, ops, workspace, name, splits)
     _req_bias(bias, N, name)
     q_out, kv8 = _rope_kv_args(name, M, N, pos, slot, cos_sin, k_cache, v_cache, n_q_heads, q_out)
     slots, Hkv, max_seq, D = k_cache.shape
+    qk_norm = _req_qk_norm(qk_norm, D, name)
     fam.launch(ops, workspace, *dims)
+    if qk_norm is not None:
+        qw, kw, neps = qk_norm
+        _check(lib().dmcp_reduce_rope_kv_norm(_ptr(workspace), S, _ptr(pos), _ptr(slot), _ptr(cos_sin), _ptr(q_out),
+                                              _ptr(k_cache), _ptr(v_cache), M, n_q_heads, Hkv, D, max_seq,
+                                              cos_sin.shape[0], slots, kv8, _stream(), _ptr(bias), _ptr(qw), _ptr(kw),
+                                              neps), "dmcp_reduce_rope_kv_norm")
+        return q_out
     _check(lib().dmcp_reduce_rope_kv(_ptr(workspace), S, _ptr(pos), _ptr(slot), _ptr(cos_sin), _ptr(q_out),
                                      _ptr(k_cache), _ptr(v_cache), M, n_q_heads, Hkv, D, max_seq, cos_sin.shape[0],
                                      slots, kv8, _stream(), _ptr(bias)), "dmcp_reduce_rope_kv")

@@ -98,10 +98,24 @@ def rope_inv_freq(head_dim: int, theta: float = 10000.0, scaling=None) -> torch.
     return torch.where(is_mid, mid, out).to(torch.float64)
 
 
-def rope_tables(max_pos: int, head_dim: int, theta: float = 10000.0, device=None, scaling=None) -> torch.Tensor:
+def rope_tables(max_pos: int, head_dim: int, theta: float = 10000.0, device=None, scaling=None,
+                fp32_angles: bool = False) -> torch.Tensor:
     """[max_pos, D/2, 2] float32 (cos, sin) -- viewed as float2 by the kernel.
     ``scaling``: a ``rope_scaling`` dict (or its :func:`rope_scaling_key`
-    form) of type "linear" or "llama3"; None = the plain ``theta`` table."""
+    form) of type "linear" or "llama3"; None = the plain ``theta`` table.
+    ``fp32_angles``: frequencies, angles and cos / sin in fp32, the way the
+    checkpoints' own code computes them (position x inv_freq rounded to fp32:
+    up to 3e-5 rad at position 1,000).  QK-norm models use it: their unit-RMS
+    q / k turn that angle rounding into attention-logit differences ~40x the
+    fp32 noise of an un-normed model (tests/test_checkpoint_qwen3.py)."""
+    if fp32_angles:
+        half = head_dim // 2
+        if rope_scaling_key(scaling) is None:
+            f = 1.0 / (theta ** (torch.arange(0, 2 * half, 2, dtype=torch.int64).to(torch.float32) / (2 * half)))
+        else:
+            f = rope_inv_freq(head_dim, theta, scaling).to(torch.float32)  # evaluated in fp32: exact
+        ang = torch.arange(max_pos, dtype=torch.float32)[:, None] * f[None, :]
+        return torch.stack([ang.cos(), ang.sin()], dim=-1).to(device)
     inv = rope_inv_freq(head_dim, theta, scaling)
     ang = torch.arange(max_pos, dtype=torch.float64)[:, None] * inv[None, :]
     return torch.stack([ang.cos(), ang.sin()], dim=-1).to(torch.float32).to(device)
@@ -119,14 +133,27 @@ def apply_rope(x: torch.Tensor, pos: torch.Tensor, cos_sin: torch.Tensor) -> tor
     return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1)
 
 
+def head_rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float) -> torch.Tensor:
+    """RMSNorm over the last axis of x [T, H, D] with one weight [D] for all
+    heads (QK-norm): fp32 in and out, no rounding."""
+    xf = x.float()
+    return xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * weight.float()
+
+
 def rope_kv(qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
-            k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, q_out: Optional[torch.Tensor] = None
-            ) -> torch.Tensor:
+            k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, q_out: Optional[torch.Tensor] = None,
+            qk_norm: Optional[tuple] = None) -> torch.Tensor:
+    """``qk_norm`` (q_weight [D], k_weight [D], eps): per-head RMSNorm of the q
+    and k heads in fp32 between the projection and the rotation."""
     S, Hkv, MAXS, D = k_cache.shape
     T = qkv.shape[0]
     x = qkv.view(T, n_q_heads + 2 * Hkv, D)
-    q = apply_rope(x[:, :n_q_heads], pos, cos_sin).to(qkv.dtype)
-    k = apply_rope(x[:, n_q_heads:n_q_heads + Hkv], pos, cos_sin).to(qkv.dtype)
+    xq, xk = x[:, :n_q_heads], x[:, n_q_heads:n_q_heads + Hkv]
+    if qk_norm is not None:
+        qw, kw, neps = qk_norm
+        xq, xk = head_rmsnorm(xq, qw, neps), head_rmsnorm(xk, kw, neps)
+    q = apply_rope(xq, pos, cos_sin).to(qkv.dtype)
+    k = apply_rope(xk, pos, cos_sin).to(qkv.dtype)
     v = x[:, n_q_heads + Hkv:]
     for t in range(T):
         p, s = int(pos[t]), int(slot[t])
@@ -147,30 +174,34 @@ def _linear_f32(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]) 
 def fused_rope_kv(x: torch.Tensor, w: torch.Tensor, eps: float, pos: torch.Tensor, slot: torch.Tensor,
                   cos_sin: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int,
                   q_out: Optional[torch.Tensor] = None, wk: int = 8,
-                  bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None) -> torch.Tensor:
     """rope_kv(rms(x) . w^T + bias) with the product kept in fp32 up to RoPE
-    (the fused kernel rotates its accumulator); ``wk`` is the kernel's."""
+    (the fused kernel rotates its accumulator); ``wk`` is the kernel's.
+    ``qk_norm`` is part of this CPU model only: the HIP kernel takes none."""
     xf = x.float()
     xn = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
-    return rope_kv(_linear_f32(xn, w, bias), pos, slot, cos_sin, k_cache, v_cache, n_q_heads, q_out
-                   ).to(torch.bfloat16)
+    return rope_kv(_linear_f32(xn, w, bias), pos, slot, cos_sin, k_cache, v_cache, n_q_heads, q_out,
+                   qk_norm=qk_norm).to(torch.bfloat16)
 
 
 def wgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
                   k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, workspace=None,
                   q_out: Optional[torch.Tensor] = None, splits: int = 0,
-                  bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None) -> torch.Tensor:
     """rope_kv(bf16(x . w^T + bias)): the split-K reduction rounds the biased
-    fp32 sum to bf16 before RoPE (what F.linear + rope_kv compute)."""
-    return rope_kv(_linear_f32(x, w, bias).to(torch.bfloat16), pos, slot, cos_sin, k_cache, v_cache, n_q_heads, q_out)
+    fp32 sum to bf16 before the QK-norm and RoPE (what F.linear + rope_kv
+    compute)."""
+    return rope_kv(_linear_f32(x, w, bias).to(torch.bfloat16), pos, slot, cos_sin, k_cache, v_cache, n_q_heads, q_out,
+                   qk_norm=qk_norm)
 
 
 def tgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
                   k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, workspace=None,
                   q_out: Optional[torch.Tensor] = None, splits: int = 0,
-                  bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None) -> torch.Tensor:
     """The same composition as :func:`wgemm_rope_kv` (one reduction serves both)."""
-    return wgemm_rope_kv(x, w, pos, slot, cos_sin, k_cache, v_cache, n_q_heads, workspace, q_out, splits, bias)
+    return wgemm_rope_kv(x, w, pos, slot, cos_sin, k_cache, v_cache, n_q_heads, workspace, q_out, splits, bias,
+                         qk_norm)
 
 
 class SharedPrefix(NamedTuple):

@@ -441,7 +441,7 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
                      intermediate: int = 8192, vocab: int = 128256, tokenizer: str = "code-bpe-128k",
                      outliers=(7, 300, 1029, 1800), seed: int = 11, device: str = "cuda", rope_scaling=None,
                      qkv_bias: bool = False, model_type: Optional[str] = None, tie_embeddings: bool = False,
-                     head_dim: Optional[int] = None) -> str:
+                     head_dim: Optional[int] = None, qk_norm: bool = False) -> str:
     """A Llama-format checkpoint directory (``config.json``, one
     ``model.safetensors``, ``tokenizer.json``) with *trained-like* random
     weights -- no download exists here: heavy-tailed matrices (a Gaussian
@@ -457,7 +457,11 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
     checkpoint's layout with values no loader can drop unnoticed, far from
     fp8 saturation.  ``model_type="qwen2"`` writes the Qwen2 config keys;
     ``tie_embeddings`` omits ``lm_head.weight``; ``head_dim`` decouples the
-    head width from hidden / heads."""
+    head width from hidden / heads.  ``qk_norm``: per-head ``q_norm`` /
+    ``k_norm`` weights [head_dim] drawn like the other norm weights (1 +- 0.25)
+    after every other draw -- the Qwen3 layout; ``model_type="qwen3"`` writes
+    the Qwen3 config keys (``head_dim``, ``layer_types``, ``attention_bias``,
+    ``use_sliding_window``, ``rope_theta`` 1e6)."""
     import gzip
     import json
 
@@ -500,6 +504,11 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
             for n, rows in (("q", heads * hd), ("k", kv_heads * hd), ("v", kv_heads * hd)):
                 b = 2.0 * torch.randn(rows, generator=g, device=device)
                 t[p + f"self_attn.{n}_proj.bias"] = b.to(torch.bfloat16).cpu()
+    if qk_norm:  # drawn last: every tensor above is what a call without it writes
+        for i in range(layers):
+            for n in ("q_norm", "k_norm"):
+                w = 1.0 + 0.25 * torch.randn(hd, generator=g, device=device)
+                t[f"model.layers.{i}.self_attn.{n}.weight"] = w.to(torch.bfloat16).cpu()
     if tie_embeddings:
         del t["lm_head.weight"]
     save_file(t, os.path.join(root, "model.safetensors"))
@@ -510,9 +519,13 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
     if model_type == "qwen2":
         cfg.update({"model_type": "qwen2", "architectures": ["Qwen2ForCausalLM"], "hidden_act": "silu",
                     "use_sliding_window": False, "attention_dropout": 0.0})
+    elif model_type == "qwen3":
+        cfg.update({"model_type": "qwen3", "architectures": ["Qwen3ForCausalLM"], "hidden_act": "silu",
+                    "head_dim": hd, "layer_types": ["full_attention"] * layers, "attention_bias": bool(qkv_bias),
+                    "use_sliding_window": False, "attention_dropout": 0.0, "rope_theta": 1000000.0})
     elif model_type is not None:
         cfg["model_type"] = model_type
-    if qkv_bias and model_type != "qwen2":
+    if qkv_bias and model_type not in ("qwen2", "qwen3"):
         cfg["attention_bias"] = True
     if head_dim is not None:
         cfg["head_dim"] = head_dim
