@@ -77,6 +77,12 @@ class Config:
     local_llm_method_max_bytes: int = 0
     local_llm_step_max_bytes: int = 0
     local_llm_max_steps: int = 0
+    # selection temperature of the local model: 0 = greedy (every token the
+    # argmax under the grammar mask); above 0 each token is a draw from
+    # softmax(logits / T) over the allowed ids, reproducible for a seed
+    # (dmcp/ops/reference.py gumbel_noise).  Every worker uses the same seed.
+    local_llm_temperature: float = 0.0
+    local_llm_seed: int = 0
     local_llm_devices: str = "all"
     # "process": one worker process per GPU, started before this process
     # touches HIP (the service default); "inline": engines in this process
@@ -154,6 +160,8 @@ class Config:
             "LOCAL_LLM_METHOD_MAX_BYTES": "local_llm_method_max_bytes",
             "LOCAL_LLM_STEP_MAX_BYTES": "local_llm_step_max_bytes",
             "LOCAL_LLM_MAX_STEPS": "local_llm_max_steps",
+            "LOCAL_LLM_TEMPERATURE": "local_llm_temperature",
+            "LOCAL_LLM_SEED": "local_llm_seed",
             "LOCAL_LLM_DEVICES": "local_llm_devices",
             "LOCAL_LLM_WORKERS": "local_llm_workers",
             "LOCAL_LLM_MAX_BATCH": "local_llm_max_batch",

@@ -42,6 +42,7 @@ from __future__ import annotations
 import gc
 import json
 import logging
+import math
 import os
 import threading
 import time
@@ -512,8 +513,21 @@ class LocalEngine:
                  max_new_tokens: Optional[int] = None, native_grammar: Optional[bool] = None,
                  fork_methods: bool = True, fork_max_context: int = 0,
                  reply_shape: Optional[ReplyShape] = None, type_choice: Optional[bool] = None,
-                 precapture: Optional[bool] = None) -> None:
+                 precapture: Optional[bool] = None, temperature: float = 0.0, seed: int = 0) -> None:
         self.model = model
+        # temperature 0 (the default) is the greedy selection, unchanged; above
+        # it every selected token -- the decode steps' and the first one after
+        # a prefill -- is a draw from softmax(logits / temperature) over the
+        # ids the grammar allows, a function of (seed, KV slot, position)
+        # only (dmcp.ops.masked_sample): the same seed and the same schedule
+        # give the same replies
+        temperature = float(temperature)
+        if not math.isfinite(temperature) or temperature < 0:
+            raise ValueError(f"temperature must be finite and >= 0, got {temperature!r}")
+        self.temperature = temperature
+        self.seed = int(seed)
+        self._sample = (temperature, self.seed & 0xFFFFFFFF) if temperature > 0 else None
+        self._sample_kw = {"sample": self._sample} if self._sample is not None else {}
         self.tok = tokenizer if tokenizer is not None else ByteTokenizer(model.cfg.vocab_size)
         self._tb = self.tok.token_bytes
         self._quote = self.tok.quote
@@ -561,7 +575,7 @@ class LocalEngine:
         self._choice_rows: Dict[Tuple[int, bytes], int] = {}
         masks = list(self.tok.json_masks(self.cfg.vocab_size)) + self._choice_masks()
         self.masks = torch.tensor(masks, dtype=torch.int32, device=dev)
-        self.graphs = DecodeGraphs(model, self.masks, alt_token=self._quote) \
+        self.graphs = DecodeGraphs(model, self.masks, alt_token=self._quote, **self._sample_kw) \
             if use_graphs and dev.type == "cuda" else None
         # every row-count bucket's decode graph captured now, at engine start:
         # captured on first use instead, the larger buckets' captures (~15 ms
@@ -946,7 +960,7 @@ class LocalEngine:
         from .. import ops
         t0 = time.perf_counter()
         reqs = []
-        need, midx_l = [], []
+        need, midx_l, keys_l = [], [], []
         for i, s in enumerate(batch):
             first = s.segs[0].ids or []
             toks = s.prompt + first
@@ -967,6 +981,7 @@ class LocalEngine:
             if m is not None:
                 need.append(i)
                 midx_l.append(m)
+                keys_l.append((s.slot, len(toks) - 1))  # the last prefilled token: no decode row of the slot has it
         dev = self.model.device
         h = {"batch": batch, "need": need, "ids": None, "event": None}
         timed = dev.type == "cuda"
@@ -983,7 +998,16 @@ class LocalEngine:
             if dev.type == "cuda":  # no pageable (host-blocking) copy behind the prefill
                 midx = midx.pin_memory()
             midx = midx.to(dev, non_blocking=True)
-            ids = ops.masked_argmax(rows.contiguous(), self.masks, vocab=self.cfg.vocab_size, mask_idx=midx)
+            if self._sample is not None:
+                keys = torch.tensor(keys_l, dtype=torch.int32).t().contiguous()
+                if dev.type == "cuda":
+                    keys = keys.pin_memory()
+                keys = keys.to(dev, non_blocking=True)
+                ids = ops.masked_sample(rows.contiguous(), self.masks, vocab=self.cfg.vocab_size, mask_idx=midx,
+                                        slots=keys[0], positions=keys[1], temperature=self._sample[0],
+                                        seed=self._sample[1])
+            else:
+                ids = ops.masked_argmax(rows.contiguous(), self.masks, vocab=self.cfg.vocab_size, mask_idx=midx)
             host = torch.empty(len(need), dtype=torch.int32, pin_memory=dev.type == "cuda")
             host.copy_(ids, non_blocking=dev.type == "cuda")
             h["ids"] = host
@@ -1042,7 +1066,7 @@ class LocalEngine:
             _, ids = self.model.decode_select_gather(t[0].contiguous(), t[4].contiguous(), self._last_ids,
                                                      t[1].contiguous(), t[2].contiguous(), self.masks,
                                                      t[3].contiguous(), t[5].contiguous(), self._quote,
-                                                     t[6].contiguous())
+                                                     t[6].contiguous(), **self._sample_kw)
         host = self._host_ids[buf]
         host[:n].copy_(ids[:n], non_blocking=self.model.device.type == "cuda")
         if self.model.device.type == "cuda":
@@ -1064,7 +1088,7 @@ class LocalEngine:
             _, ids = self.model.decode_select_gather(t[0].contiguous(), t[4].contiguous(), self._last_ids,
                                                      t[1].contiguous(), t[2].contiguous(), self.masks,
                                                      t[3].contiguous(), t[5].contiguous(), self._quote,
-                                                     t[6].contiguous())
+                                                     t[6].contiguous(), **self._sample_kw)
         n = len(toks)
         host = self._host_ids[buf]
         host[:n].copy_(ids[:n], non_blocking=self.model.device.type == "cuda")

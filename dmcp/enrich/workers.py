@@ -669,7 +669,9 @@ def engine_spec(cfg) -> dict:
             "reply_shape": {"desc": int(getattr(cfg, "local_llm_desc_max_bytes", 0)),
                             "method": int(getattr(cfg, "local_llm_method_max_bytes", 0)),
                             "step": int(getattr(cfg, "local_llm_step_max_bytes", 0)),
-                            "max_steps": int(getattr(cfg, "local_llm_max_steps", 0))}}
+                            "max_steps": int(getattr(cfg, "local_llm_max_steps", 0))},
+            "temperature": float(getattr(cfg, "local_llm_temperature", 0.0)),
+            "seed": int(getattr(cfg, "local_llm_seed", 0))}
 
 
 # ------------------------------------------------------------------ child

@@ -1129,41 +1129,54 @@ class LocalLM:
         self._fork_set([(int(x), int(x), 0) for x in slots])
 
     def decode_select(self, tokens: torch.Tensor, slots: torch.Tensor, positions: torch.Tensor,
-                      masks: torch.Tensor, mask_idx: torch.Tensor) -> tuple:
-        """:meth:`decode` + greedy selection under a per-row grammar mask
-        (``masks`` [M, ceil(V/32)] bitsets, ``mask_idx`` int32 [B]).
+                      masks: torch.Tensor, mask_idx: torch.Tensor, sample: Optional[tuple] = None) -> tuple:
+        """:meth:`decode` + selection under a per-row grammar mask
+        (``masks`` [M, ceil(V/32)] bitsets, ``mask_idx`` int32 [B]): greedy,
+        or with ``sample`` = (temperature, seed) a draw from softmax(logits /
+        temperature) over the allowed ids, keyed by the row's slot and
+        position (:func:`dmcp.ops.masked_sample`; temperature 0 is greedy).
         Returns (logits, ids int32 [B]); capturable."""
         logits = self.decode(tokens, slots, positions)
-        ids = ops.masked_argmax(logits, masks, vocab=self.cfg.vocab_size, mask_idx=mask_idx)
+        if sample is not None:
+            ids = ops.masked_sample(logits, masks, vocab=self.cfg.vocab_size, mask_idx=mask_idx, slots=slots,
+                                    positions=positions, temperature=sample[0], seed=sample[1])
+        else:
+            ids = ops.masked_argmax(logits, masks, vocab=self.cfg.vocab_size, mask_idx=mask_idx)
         return logits, ids
 
     def decode_select_gather(self, tokens: torch.Tensor, src: torch.Tensor, last_ids: torch.Tensor,
                              slots: torch.Tensor, positions: torch.Tensor, masks: torch.Tensor,
                              mask_idx: torch.Tensor, mask_alt: Optional[torch.Tensor] = None,
-                             alt_token: int = -1, prefix_rows: Optional[torch.Tensor] = None) -> tuple:
+                             alt_token: int = -1, prefix_rows: Optional[torch.Tensor] = None,
+                             sample: Optional[tuple] = None) -> tuple:
         """:meth:`decode_select` whose input token of row r is ``last_ids[src[r]]``
         where ``src[r] >= 0`` (the previous step's selection, still on the
         device) and ``tokens[r]`` otherwise; the step's own selections are
         written to ``last_ids`` for the next step.  Lets the host launch step
         t+1 before it has read step t's ids (the engine's one-step pipeline).
         ``mask_alt`` / ``alt_token`` / ``prefix_rows``: see :meth:`decode`.
+        ``sample`` = (temperature, seed): every path samples instead (the
+        same tiles and launches: the selection kernels' sampling variants).
         Capturable."""
         B = tokens.shape[0]
+        keys = {} if sample is None else {"slots": slots, "positions": positions, "temperature": sample[0],
+                                          "seed": sample[1]}
         if self.fused_head and not (self.use_fused and B <= self.fused_max_rows):
             # the LM head + grammar-masked selection in one weight-streaming
             # kernel: no [B, vocab] logits (returned as None)
             h = self._decode_trunk(tokens, slots, positions, src, last_ids, mask_idx, mask_alt, alt_token,
                                    prefix_rows)
             if self.tg_head and B >= self.TGEMM_HEAD_MIN_ROWS:
-                ids = ops.tgemm_lm_head_argmax(h, self.w["lm_head"], masks, mask_idx, out=last_ids[:B],
-                                               workspace=self.tg_head_ws)
+                head = ops.tgemm_lm_head_argmax if sample is None else ops.tgemm_lm_head_sample
+                ids = head(h, self.w["lm_head"], masks, mask_idx, out=last_ids[:B], workspace=self.tg_head_ws, **keys)
             else:
-                ids = ops.lm_head_argmax(h, self.w["lm_head"], masks, mask_idx, out=last_ids[:B],
-                                         workspace=self.head_ws)
+                head = ops.lm_head_argmax if sample is None else ops.lm_head_sample
+                ids = head(h, self.w["lm_head"], masks, mask_idx, out=last_ids[:B], workspace=self.head_ws, **keys)
             return None, ids
         logits = self.decode(tokens, slots, positions, src=src, last_ids=last_ids, mask_idx=mask_idx,
                              mask_alt=mask_alt, alt_token=alt_token, prefix_rows=prefix_rows)
-        ids = ops.masked_argmax(logits, masks, vocab=self.cfg.vocab_size, mask_idx=mask_idx, out=last_ids[:B])
+        select = ops.masked_argmax if sample is None else ops.masked_sample
+        ids = select(logits, masks, vocab=self.cfg.vocab_size, mask_idx=mask_idx, out=last_ids[:B], **keys)
         return logits, ids
 
     # reference path (pure torch, fp32 math) for numerics tests
@@ -1270,17 +1283,21 @@ class DecodeGraphs:
     ``alt_token``, uses-the-shared-prefix flag) -> one H2D copy into the graph's static
     input; the graph gathers the rows whose source is >= 0 from the previous
     step's selections (:attr:`last_ids`, device-resident, written by every
-    step), runs the whole forward plus the masked argmax, so a step costs one
+    step), runs the whole forward plus the masked selection, so a step costs one
     copy in, one replay and one 4-byte-per-row copy out.  Padding rows carry
     slot -1 (kernels skip them).  Returned tensors are the graph's static
     outputs: read them before the next replay of the same bucket."""
 
     def __init__(self, model: LocalLM, masks: torch.Tensor,
                  buckets: Sequence[int] = (1, 2, 4, 8, 16, 32, 64, 96, 128, 192, 256, 320, 384, 448, 512, 640,
-                                          768, 896, 1024), alt_token: int = -1) -> None:
+                                          768, 896, 1024), alt_token: int = -1,
+                 sample: Optional[tuple] = None) -> None:
         self.model = model
         self.masks = masks
         self.alt_token = int(alt_token)
+        # (temperature, seed) of a sampling engine, fixed for its lifetime: a
+        # constant of the captured selection kernels (None: greedy)
+        self.sample = sample
         self.timing = {"sync_s": 0.0, "replay_s": 0.0}  # host time inside run(): staging wait, H2D + launch
         # device witness: graph replays and the kernel nodes they launched
         self.counts = {"graph_replays": 0, "graph_kernels": 0}
@@ -1322,14 +1339,14 @@ class DecodeGraphs:
         with torch.cuda.stream(s):
             for _ in range(2):  # warm up hipBLASLt heuristics / allocator outside capture
                 m.decode_select_gather(inp[0], inp[4], scratch, inp[1], inp[2], self.masks, inp[3], inp[5],
-                                       self.alt_token, inp[6])
+                                       self.alt_token, inp[6], self.sample)
         torch.cuda.current_stream().wait_stream(s)
         # keep_graph: the hipGraph_t stays queryable after capture (the kernel
         # node count of the witness); instantiated explicitly right after
         g = torch.cuda.CUDAGraph(keep_graph=True)
         with torch.cuda.graph(g):
             logits, ids = m.decode_select_gather(inp[0], inp[4], self.last_ids, inp[1], inp[2], self.masks, inp[3],
-                                                 inp[5], self.alt_token, inp[6])
+                                                 inp[5], self.alt_token, inp[6], self.sample)
         bucket = _Bucket(g, inp, logits, ids, b)
         g.instantiate()
         self.graphs[b] = bucket
@@ -1356,7 +1373,7 @@ class DecodeGraphs:
                               list(prefix_rows)], dtype=torch.int32, device=m.device)
             return m.decode_select_gather(t[0].contiguous(), t[4].contiguous(), self.last_ids, t[1].contiguous(),
                                           t[2].contiguous(), self.masks, t[3].contiguous(), t[5].contiguous(),
-                                          self.alt_token, t[6].contiguous())
+                                          self.alt_token, t[6].contiguous(), self.sample)
         b = self.bucket_for(n)
         if b not in self.graphs:
             self._capture(b)

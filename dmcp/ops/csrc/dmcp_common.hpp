@@ -208,6 +208,55 @@ __device__ __forceinline__ void sum_slices8(const float* __restrict__ part, int 
     }
 }
 
+// ---- temperature sampling as a perturbed argmax (Gumbel-max): the id with
+// the highest bf16(logit) / T + g_v, g_v independent standard Gumbel noise, is
+// an exact sample of softmax(logits / T) over the allowed ids, so the
+// selection kernels keep their tiles, pair reduction and launch count.  The
+// noise is a counter-based hash of (seed, slot, position, id) in uint32
+// arithmetic -- the same bits here and in dmcp/ops/reference.py gumbel_bits:
+//   key(row)     = fmix32(seed ^ fmix32(slot * 0x9E3779B1 + position))
+//   bits(row, v) = fmix32(key(row) + v * 0x9E3779B1)
+//   u = ((bits >> 9) + 0.5) * 2^-23   (exact in fp32, inside (0, 1))
+//   g = -log(-log(u))                 (logf, not the fast intrinsic)
+__device__ __forceinline__ uint32_t fmix32(uint32_t h) {  // MurmurHash3's finaliser
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h;
+}
+
+__device__ __forceinline__ uint32_t gumbel_key(uint32_t seed, int slot, int position) {
+    return fmix32(seed ^ fmix32((uint32_t)slot * 0x9E3779B1u + (uint32_t)position));
+}
+
+// score of id v: x (a bf16-rounded logit) / T + g_v; one call per ALLOWED id
+// (two logs: callers skip the ids their mask excludes)
+__device__ __forceinline__ float gumbel_score(float x, float inv_t, uint32_t key, int v) {
+    const uint32_t bits = fmix32(key + (uint32_t)v * 0x9E3779B1u);
+    const float u = (float)((bits >> 9) * 2u + 1u) * 0x1p-24f;  // (2 k + 1) / 2^24, k < 2^23: exact
+    return fmaf(x, inv_t, -logf(-logf(u)));
+}
+
+// The sampling variants' extra kernel argument (per-row keys: the step's
+// slots and positions); the greedy instantiations take an empty struct, so
+// their code does not change.  Rows with slot < 0 (padding) draw nothing.
+struct SampleKeys {
+    const int32_t* slots;
+    const int32_t* positions;
+    uint32_t seed;
+    float inv_t;
+};
+struct NoSampleKeys {};
+template <bool SAMPLE>
+using sample_keys_t = std::conditional_t<SAMPLE, SampleKeys, NoSampleKeys>;
+template <bool SAMPLE>
+inline sample_keys_t<SAMPLE> pick_keys(const SampleKeys& sk) {
+    if constexpr (SAMPLE) return sk;
+    else return {};
+}
+
 // The LM head's per-row selection from per-tile (max, id) pairs (wgemm.hip /
 // tgemm.hip MODE_ARGMAX write best[tile * M + row]): the highest value, the
 // lowest id among ties; 0 when the mask allowed nothing (as masked_argmax).

@@ -334,11 +334,30 @@ __device__ __forceinline__ void argmax_take(float x, int v, float& best, int& bi
 // past the last whole chunk take the element-wise loop.
 constexpr int MA_T = 1024, MA_U = 2;
 
+//
+// SAMPLE: temperature sampling as a perturbed argmax (dmcp_common.hpp
+// gumbel_score): every allowed id's value becomes value / T + Gumbel noise
+// keyed by (seed, the row's slot, its position, the id) -- the hash and the
+// two logs only for the ids the mask allows; a row with slot < 0 selects 0.
+// The greedy instantiation takes an empty struct and compiles as before.
+template <bool SAMPLE>
 __global__ __launch_bounds__(MA_T) void masked_argmax_kernel(const uint16_t* __restrict__ logits,
                                                             const uint32_t* __restrict__ mask,
                                                             const int32_t* __restrict__ mask_idx, int n_masks,
-                                                            int32_t* __restrict__ ids, int V, int ld, int nch) {
+                                                            int32_t* __restrict__ ids, int V, int ld, int nch,
+                                                            sample_keys_t<SAMPLE> sk) {
     const int b = blockIdx.x;
+    uint32_t key = 0;
+    float inv_t = 1.f;
+    if constexpr (SAMPLE) {
+        const int slot = sk.slots[b];
+        if (slot < 0) {  // block-uniform: a padding row
+            if (threadIdx.x == 0) ids[b] = 0;
+            return;
+        }
+        key = gumbel_key(sk.seed, slot, sk.positions[b]);  // once per row
+        inv_t = sk.inv_t;
+    }
     const uint16_t* row = logits + (size_t)b * ld;
     int mr = b;
     if (mask_idx) {
@@ -367,7 +386,12 @@ __global__ __launch_bounds__(MA_T) void masked_argmax_kernel(const uint16_t* __r
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 float x = __uint_as_float((j & 1) ? (w[j >> 1] & 0xFFFF0000u) : (w[j >> 1] << 16));
-                x = ((m >> j) & 1u) ? x : -INFINITY;
+                if constexpr (SAMPLE) {
+                    if ((m >> j) & 1u) x = gumbel_score(x, inv_t, key, c * 8 + j);
+                    else x = -INFINITY;
+                } else {
+                    x = ((m >> j) & 1u) ? x : -INFINITY;
+                }
                 const bool t = x > bv[j];
                 bv[j] = t ? x : bv[j];
                 bc[j] = t ? c : bc[j];
@@ -381,7 +405,9 @@ __global__ __launch_bounds__(MA_T) void masked_argmax_kernel(const uint16_t* __r
         if (bc[j] != 0x0fffffff) argmax_take(bv[j], bc[j] * 8 + j, best, bi);
     for (int v = nch * 8 + threadIdx.x; v < V; v += MA_T) {
         if (mrow && !((mrow[v >> 5] >> (v & 31)) & 1u)) continue;
-        argmax_take(bf2f(row[v]), v, best, bi);
+        float x = bf2f(row[v]);
+        if constexpr (SAMPLE) x = gumbel_score(x, inv_t, key, v);
+        argmax_take(x, v, best, bi);
     }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
@@ -1100,9 +1126,25 @@ int dmcp_masked_argmax(const void* logits, const void* mask, const void* mask_id
     if (mask_idx && n_masks <= 0) return hipErrorInvalidValue;
     // whole 16-B chunks only when every row start is 16-B aligned
     const bool vec = (ld % 8 == 0) && (reinterpret_cast<uintptr_t>(logits) % 16 == 0);
-    masked_argmax_kernel<<<B, MA_T, 0, (hipStream_t)stream>>>((const uint16_t*)logits, (const uint32_t*)mask,
-                                                             (const int32_t*)mask_idx, n_masks, (int32_t*)ids, V,
-                                                             ld, vec ? V / 8 : 0);
+    masked_argmax_kernel<false><<<B, MA_T, 0, (hipStream_t)stream>>>(
+        (const uint16_t*)logits, (const uint32_t*)mask, (const int32_t*)mask_idx, n_masks, (int32_t*)ids, V, ld,
+        vec ? V / 8 : 0, NoSampleKeys{});
+    return hipGetLastError();
+}
+
+// dmcp_masked_argmax at a temperature: ids[b] = argmax over the allowed v of
+// bf16 logit * inv_temperature + Gumbel noise keyed by (seed, slots[b],
+// positions[b], v) (dmcp_common.hpp); rows with slots[b] < 0 select 0.
+int dmcp_masked_sample(const void* logits, const void* mask, const void* mask_idx, int n_masks, void* ids, int B,
+                       int V, int ld, const void* slots, const void* positions, unsigned seed, float inv_temperature,
+                       void* stream) {
+    if (B <= 0) return 0;
+    if ((mask_idx && n_masks <= 0) || !slots || !positions || !(inv_temperature > 0.f)) return hipErrorInvalidValue;
+    const bool vec = (ld % 8 == 0) && (reinterpret_cast<uintptr_t>(logits) % 16 == 0);
+    const SampleKeys sk{(const int32_t*)slots, (const int32_t*)positions, seed, inv_temperature};
+    masked_argmax_kernel<true><<<B, MA_T, 0, (hipStream_t)stream>>>(
+        (const uint16_t*)logits, (const uint32_t*)mask, (const int32_t*)mask_idx, n_masks, (int32_t*)ids, V, ld,
+        vec ? V / 8 : 0, sk);
     return hipGetLastError();
 }
 

@@ -38,7 +38,10 @@
 //     splitk_reduce.hip (RoPE + KV append, residual + RMSNorm);
 //   * MODE_ARGMAX: the LM head + grammar-masked greedy selection (per block
 //     and row one (max, id) pair per 64 vocabulary ids, a per-row
-//     reduction kernel selects), no [M, V] logits.
+//     reduction kernel selects), no [M, V] logits;
+//   * TM_SAMPLE: TM_ARGMAX at a temperature -- each allowed id's value
+//     perturbed in the epilogue with Gumbel noise (dmcp_common.hpp
+//     gumbel_score) keyed by the row's slot and position.
 #include "dmcp_common.hpp"
 
 namespace {
@@ -72,7 +75,7 @@ __device__ __forceinline__ void wait_vm(int n) {
 }
 constexpr int TNB = 256;  // weight rows per block
 constexpr int TTH = 512;  // threads per block: 8 waves, two per SIMD
-constexpr int TM_BF16 = 0, TM_PART = 1, TM_SWIGLU = 2, TM_ARGMAX = 3;
+constexpr int TM_BF16 = 0, TM_PART = 1, TM_SWIGLU = 2, TM_ARGMAX = 3, TM_SAMPLE = 4;
 
 // slot of logical 16-B chunk j of image row r (128-B rows, 8 chunks): the
 // 16 lanes of each ds_read_b128 group of the 16x16x32 operand layout (lane
@@ -90,7 +93,7 @@ template <int XT, int MODE, int PROBE = 0>
 __global__ __launch_bounds__(TTH) __attribute__((amdgpu_waves_per_eu(2, 2))) void tgemm_kernel(
     const uint16_t* __restrict__ x, const uint16_t* __restrict__ w, uint16_t* __restrict__ y, float* __restrict__ part,
     int M, int N, int K, int cps, int S, int ntiles, int mparts, int mrows, int I, const uint32_t* __restrict__ masks,
-    const int32_t* __restrict__ midx, int n_masks, int wwords) {
+    const int32_t* __restrict__ midx, int n_masks, int wwords, sample_keys_t<MODE == TM_SAMPLE> sk) {
     constexpr int NF = TNB / 64;       // A fragments per wave (16 weight rows each): a quarter of the tile's rows
     constexpr int RCH = TKC / 8;       // 16-B chunks per image row
     constexpr int PR = 64 / RCH;       // image rows per 1-KiB LDS-DMA piece
@@ -260,10 +263,22 @@ __global__ __launch_bounds__(TTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int t = 0; t < XT; ++t) {
         if (t >= mtv) continue;
         const int m = m_lo + mw + 16 * t + l16;
-        if constexpr (MODE == TM_ARGMAX) {
+        if constexpr (MODE == TM_ARGMAX || MODE == TM_SAMPLE) {
+            // TM_SAMPLE perturbs each allowed value (row key once per row, no
+            // hash or log for masked ids); a padding row (slot < 0) keeps
+            // the empty pair
             float bv = -INFINITY;
             int bi = 0x7fffffff;
-            if (m < m_hi) {
+            bool live = m < m_hi;
+            uint32_t key = 0;
+            if constexpr (MODE == TM_SAMPLE) {
+                if (live) {
+                    const int slot = sk.slots[m];
+                    live = slot >= 0;
+                    key = gumbel_key(sk.seed, slot, sk.positions[m]);
+                }
+            }
+            if (live) {
                 int mr = midx ? midx[m] : 0;
                 mr = mr < 0 ? 0 : (mr >= n_masks ? n_masks - 1 : mr);
                 const uint32_t* mrow = masks + (size_t)mr * wwords + (c0 >> 5);
@@ -274,7 +289,8 @@ __global__ __launch_bounds__(TTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     for (int i = 0; i < 4; ++i) {
                         const int c = 16 * f + 4 * g + i;
                         if ((word >> (c & 31)) & 1u) {
-                            const float v = bf2f(f2bf(acc[f][t][i]));
+                            float v = bf2f(f2bf(acc[f][t][i]));
+                            if constexpr (MODE == TM_SAMPLE) v = gumbel_score(v, sk.inv_t, key, c0 + c);
                             if (v > bv) { bv = v; bi = c0 + c; }  // columns ascend: strict > keeps the lowest
                         }
                     }
@@ -322,7 +338,8 @@ __global__ __launch_bounds__(TTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 template <int MODE, int PROBE = 0>
 hipError_t launch_tgemm(const uint16_t* x, const uint16_t* w, uint16_t* y, float* part, int M, int N, int K, int S,
                         int mparts, int I, hipStream_t st, const uint32_t* masks, const int32_t* midx, int n_masks,
-                        int wwords) {
+                        int wwords, const SampleKeys& sk = SampleKeys{}) {
+    const auto keys = pick_keys<MODE == TM_SAMPLE>(sk);
     const int ntiles = (MODE == TM_SWIGLU ? 2 * I : N) / TNB;
     const int mrows = (((M + mparts - 1) / mparts) + 15) & ~15;
     // staged X rows in 32-row steps (>= 64)
@@ -333,7 +350,7 @@ hipError_t launch_tgemm(const uint16_t* x, const uint16_t* w, uint16_t* y, float
     const dim3 grid((unsigned)(ntiles * S * mparts));
 #define DMCP_TG(XT)                                                                                          \
     tgemm_kernel<XT, MODE, PROBE><<<grid, TTH, 0, st>>>(x, w, y, part, M, N, K, cps, S, ntiles, mparts, mrows, I, \
-                                                        masks, midx, n_masks, wwords)
+                                                        masks, midx, n_masks, wwords, keys)
     switch (xt) {
         case 2: DMCP_TG(2); break;
         case 3: DMCP_TG(3); break;
@@ -391,6 +408,29 @@ int dmcp_tgemm(const void* x, const void* w, void* y, void* part, int M, int N, 
         }
         default: return hipErrorInvalidValue;
     }
+}
+
+// mode 3 at a temperature: ids[M] = argmax over the allowed v of
+// bf16(x . w^T) * inv_temperature + Gumbel noise keyed by (seed, slots[m],
+// positions[m], v) (dmcp_common.hpp); rows with slots[m] < 0 select 0.  Same
+// contract, workspace and pair reduction as mode 3.
+int dmcp_tgemm_sample(const void* x, const void* w, void* part, int M, int N, int K, int mparts, const void* masks,
+                      const void* midx, int n_masks, int wwords, void* ids, const void* slots, const void* positions,
+                      unsigned seed, float inv_temperature, void* stream) {
+    if (M <= 0) return 0;
+    if (!x || !w || mparts < 1 || K <= 0 || K % TKC != 0 || (((M + mparts - 1) / mparts + 15) & ~15) > 256 ||
+        N <= 0 || N % TNB != 0 || !part || !masks || !ids || n_masks < 1 || wwords < (N + 31) / 32 || !slots ||
+        !positions || !(inv_temperature > 0.f))
+        return hipErrorInvalidValue;
+    auto st = (hipStream_t)stream;
+    const SampleKeys sk{(const int32_t*)slots, (const int32_t*)positions, seed, inv_temperature};
+    hipError_t e = launch_tgemm<TM_SAMPLE>((const uint16_t*)x, (const uint16_t*)w, nullptr, (float*)part, M, N, K, 1,
+                                           mparts, 0, st, (const uint32_t*)masks, (const int32_t*)midx, n_masks,
+                                           wwords, sk);
+    if (e != hipSuccess) return e;
+    argmax_pairs_kernel<<<(M + kBlock / kWave - 1) / (kBlock / kWave), kBlock, 0, st>>>(
+        (const float2*)part, 4 * (N / TNB), M, (int32_t*)ids);
+    return hipGetLastError();
 }
 
 // diagnostics (scripts/bench_tgemm.py --probe): mode-1 partials with a part

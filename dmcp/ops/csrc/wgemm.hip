@@ -41,20 +41,24 @@
 //     (max, id) pair under the row's mask bitset (the grammar state's mask
 //     row), a tiny kernel reduces the pairs per row -- the [rows, vocab]
 //     logits never exist (at 128,256 ids and 512 rows: 131 MB written and
-//     read back per step by F.linear + masked_argmax).
+//     read back per step by F.linear + masked_argmax);
+//   * MODE_SAMPLE is MODE_ARGMAX at a temperature: the same tiles and pairs,
+//     each allowed id's value perturbed in the epilogue with Gumbel noise
+//     (dmcp_common.hpp gumbel_score) keyed by the row's slot and position.
 #include "dmcp_common.hpp"
 
 namespace {
 
 constexpr int kKC = 64;  // K per LDS stage
-constexpr int MODE_BF16 = 0, MODE_PART = 1, MODE_SWIGLU = 2, MODE_ARGMAX = 3;
+constexpr int MODE_BF16 = 0, MODE_PART = 1, MODE_SWIGLU = 2, MODE_ARGMAX = 3, MODE_SAMPLE = 4;
 
 template <int NB, int MT, int MR, int MODE, int ST, int AUXW = 0>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) void wgemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
                                                        uint16_t* __restrict__ y, float* __restrict__ part, int M, int N,
                                                        int K, int ks, int S, int ntiles, int mparts, int mrows,
                                                        int I, const uint32_t* __restrict__ masks,
-                                                       const int32_t* __restrict__ midx, int n_masks, int wwords) {
+                                                       const int32_t* __restrict__ midx, int n_masks, int wwords,
+                                                       sample_keys_t<MODE == MODE_SAMPLE> sk) {
     constexpr int NF = NB / 16;         // A fragments (16 weight rows each)
     // X rows staged per block (a multiple of 32, <= 4 waves x MT 16-row
     // tiles): the M part rounded up to 32 rows, not to 64 -- at 320 rows
@@ -219,15 +223,26 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
     for (int t = 0; t < MT; ++t) {
         if (t >= mtv) continue;
         const int m = m_lo + mw + 16 * t + l16;
-        if constexpr (MODE == MODE_ARGMAX) {
+        if constexpr (MODE == MODE_ARGMAX || MODE == MODE_SAMPLE) {
             // masked max of this row over the tile's NB columns: each lane its
             // 4 NF columns, then across the 4 lane groups g (every lane takes
             // part in the shuffles; rows past the part only skip the store).
             // Values are bf16-rounded (what F.linear + masked_argmax compare),
-            // ties go to the lowest id.
+            // ties go to the lowest id.  MODE_SAMPLE perturbs each allowed
+            // value (row key once per row, no hash or log for masked ids);
+            // a padding row (slot < 0) keeps the empty pair.
             float bv = -INFINITY;
             int bi = 0x7fffffff;
-            if (m < m_hi) {
+            bool live = m < m_hi;
+            uint32_t key = 0;
+            if constexpr (MODE == MODE_SAMPLE) {
+                if (live) {
+                    const int slot = sk.slots[m];
+                    live = slot >= 0;
+                    key = gumbel_key(sk.seed, slot, sk.positions[m]);
+                }
+            }
+            if (live) {
                 int mr = midx ? midx[m] : 0;
                 mr = mr < 0 ? 0 : (mr >= n_masks ? n_masks - 1 : mr);
                 const uint32_t* mrow = masks + (size_t)mr * wwords + (n0 >> 5);
@@ -238,7 +253,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
                     for (int i = 0; i < 4; ++i) {
                         const int c = 16 * f + 4 * g + i;
                         if ((word >> (c & 31)) & 1u) {
-                            const float x = bf2f(f2bf(acc[f][t][i]));
+                            float x = bf2f(f2bf(acc[f][t][i]));
+                            if constexpr (MODE == MODE_SAMPLE) x = gumbel_score(x, sk.inv_t, key, n0 + c);
                             if (x > bv) { bv = x; bi = n0 + c; }  // columns ascend: strict > keeps the lowest
                         }
                     }
@@ -289,7 +305,9 @@ int g_wgemm_auxw = 0;
 template <int NB, int MODE>
 hipError_t launch_wgemm(const uint16_t* x, const uint16_t* w, uint16_t* y, float* part, int M, int N, int K, int S,
                         int mparts, int I, hipStream_t st, const uint32_t* masks = nullptr,
-                        const int32_t* midx = nullptr, int n_masks = 0, int wwords = 0) {
+                        const int32_t* midx = nullptr, int n_masks = 0, int wwords = 0,
+                        const SampleKeys& sk = SampleKeys{}) {
+    const auto keys = pick_keys<MODE == MODE_SAMPLE>(sk);
     const int ntiles = (MODE == MODE_SWIGLU ? 2 * I : N) / NB;
     const int mrows = (((M + mparts - 1) / mparts) + 15) & ~15;
     const int mt = (mrows + 4 * 16 - 1) / (4 * 16);  // 16-row tiles per wave
@@ -300,10 +318,10 @@ hipError_t launch_wgemm(const uint16_t* x, const uint16_t* w, uint16_t* y, float
     do {                                                                                                        \
         if (g_wgemm_auxw == 2)                                                                                  \
             wgemm_kernel<NB, MT, MR, MODE, kStages, 2><<<grid, kBlock, 0, st>>>(                                \
-                x, w, y, part, M, N, K, ks, S, ntiles, mparts, mrows, I, masks, midx, n_masks, wwords);         \
+                x, w, y, part, M, N, K, ks, S, ntiles, mparts, mrows, I, masks, midx, n_masks, wwords, keys);   \
         else                                                                                                    \
             wgemm_kernel<NB, MT, MR, MODE, kStages><<<grid, kBlock, 0, st>>>(                                   \
-                x, w, y, part, M, N, K, ks, S, ntiles, mparts, mrows, I, masks, midx, n_masks, wwords);         \
+                x, w, y, part, M, N, K, ks, S, ntiles, mparts, mrows, I, masks, midx, n_masks, wwords, keys);   \
     } while (0)
 #define DMCP_WG(MT)                  \
     do {                             \
@@ -390,6 +408,41 @@ int dmcp_lm_head_argmax(const void* x, const void* w, const void* masks, const v
     } else {
         ntiles = V / 64;
         e = launch_wgemm<64, MODE_ARGMAX>(xx, ww, nullptr, bb, M, V, K, 1, mparts, 0, st, mk, mi, n_masks, wwords);
+    }
+    if (e != hipSuccess) return e;
+    argmax_pairs_kernel<<<(M + kBlock / kWave - 1) / (kBlock / kWave), kBlock, 0, st>>>(
+        (const float2*)best, ntiles, M, (int32_t*)ids);
+    return hipGetLastError();
+}
+
+// dmcp_lm_head_argmax at a temperature: ids[m] = argmax over the allowed v of
+// bf16(x[m] . w[v]) * inv_temperature + Gumbel noise keyed by (seed, slots[m],
+// positions[m], v) (dmcp_common.hpp) -- an exact sample of softmax(logits / T)
+// over the allowed ids; rows with slots[m] < 0 select 0.  Same contract,
+// tiles, workspace and pair reduction as the greedy entry point.
+int dmcp_lm_head_sample(const void* x, const void* w, const void* masks, const void* midx, int n_masks, int wwords,
+                        void* best, void* ids, int M, int V, int K, int mparts, const void* slots,
+                        const void* positions, unsigned seed, float inv_temperature, void* stream) {
+    if (M <= 0) return 0;
+    if (!x || !w || !masks || !best || !ids || M > 512 || n_masks < 1 || wwords < (V + 31) / 32 || mparts < 1 ||
+        K % kKC != 0 || V <= 0 || V % 64 != 0 || (((M + mparts - 1) / mparts + 15) & ~15) > 256 || !slots ||
+        !positions || !(inv_temperature > 0.f))
+        return hipErrorInvalidValue;
+    auto st = (hipStream_t)stream;
+    auto xx = (const uint16_t*)x;
+    auto ww = (const uint16_t*)w;
+    auto bb = (float*)best;
+    auto mk = (const uint32_t*)masks;
+    auto mi = (const int32_t*)midx;
+    const SampleKeys sk{(const int32_t*)slots, (const int32_t*)positions, seed, inv_temperature};
+    hipError_t e;
+    int ntiles;
+    if (V % 128 == 0) {
+        ntiles = V / 128;
+        e = launch_wgemm<128, MODE_SAMPLE>(xx, ww, nullptr, bb, M, V, K, 1, mparts, 0, st, mk, mi, n_masks, wwords, sk);
+    } else {
+        ntiles = V / 64;
+        e = launch_wgemm<64, MODE_SAMPLE>(xx, ww, nullptr, bb, M, V, K, 1, mparts, 0, st, mk, mi, n_masks, wwords, sk);
     }
     if (e != hipSuccess) return e;
     argmax_pairs_kernel<<<(M + kBlock / kWave - 1) / (kBlock / kWave), kBlock, 0, st>>>(

@@ -28,6 +28,7 @@ _lock = threading.Lock()
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
+_u = ctypes.c_uint
 ABI_VERSION = 20  # must match dmcp_abi_version() in csrc/dmcp_kernels.hip
 
 
@@ -94,9 +95,19 @@ def lib() -> ctypes.CDLL:
             "dmcp_tgemm_probe": ([_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
             "dmcp_fused_gemm": ([_i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i,
                                  _i, _i, _i, _i, _vp, _vp], _i),
+            # the selection entry points at a temperature: their greedy siblings' lists + slots, positions,
+            # seed, 1 / temperature (ahead of the stream)
+            "dmcp_masked_sample": ([_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _u, _f, _vp], _i),
+            "dmcp_lm_head_sample": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _u, _f, _vp],
+                                    _i),
+            "dmcp_tgemm_sample": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _u, _f, _vp], _i),
         }
         for name, (args, res) in sigs.items():
-            fn = getattr(L, name)
+            try:
+                fn = getattr(L, name)
+            except AttributeError:  # a library built before this entry point existed (same ABI number)
+                raise HipOpsError(f"HIP kernel library {path} has no {name}; rebuild with "
+                                  f"python -m dmcp.ops.build") from None
             fn.argtypes = args
             fn.restype = res
         if L.dmcp_abi_version() != ABI_VERSION:
@@ -578,6 +589,72 @@ def masked_argmax(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, voc
     return out
 
 
+def _req_sample(slots: Optional[torch.Tensor], positions: Optional[torch.Tensor], rows: int, temperature: float,
+                seed: int, name: str) -> tuple:
+    """The sampling arguments of the selection ops, checked before any launch:
+    ``slots`` / ``positions`` int32 [rows] (the step's own inputs: the keys of
+    each row's noise), a finite ``temperature`` >= 0.  Returns (1 / T as the
+    kernels take it -- 0.0 for the greedy temperature 0 --, seed as uint32)."""
+    try:
+        t = float(temperature)
+    except (TypeError, ValueError):
+        raise HipOpsError(f"{name}: temperature must be a number, got {temperature!r}") from None
+    if not math.isfinite(t) or t < 0:
+        raise HipOpsError(f"{name}: temperature must be finite and >= 0, got {temperature!r}")
+    for key, which in ((slots, "slots"), (positions, "positions")):
+        if not isinstance(key, torch.Tensor):
+            raise HipOpsError(f"{name}: {which} (int32 [{rows}]) is required: it keys each row's noise")
+        _req(key, torch.int32, f"{name}.{which}")
+        if key.numel() != rows:
+            raise HipOpsError(f"{name}: {which} holds {key.numel()} entries for {rows} rows")
+    with np.errstate(over="ignore", under="ignore"):
+        inv_t = float(np.float32(1.0 / t)) if t > 0 else 0.0
+    if t > 0 and not (math.isfinite(inv_t) and inv_t > 0):
+        raise HipOpsError(f"{name}: 1 / temperature is not a positive fp32 number (temperature {temperature!r})")
+    return inv_t, int(seed) & 0xFFFFFFFF
+
+
+def masked_sample(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, vocab: Optional[int] = None,
+                  out: Optional[torch.Tensor] = None, mask_idx: Optional[torch.Tensor] = None,
+                  slots: Optional[torch.Tensor] = None, positions: Optional[torch.Tensor] = None,
+                  temperature: float = 0.0, seed: int = 0) -> torch.Tensor:
+    """:func:`masked_argmax` at a ``temperature``: ids[b] is a sample of
+    softmax(logits[b] / temperature) over the allowed ids, drawn as the
+    argmax of bf16 logit / T + Gumbel noise that is a hash of (``seed``,
+    ``slots[b]``, ``positions[b]``, id) (:func:`dmcp.ops.reference.gumbel_noise`):
+    a row's draw does not depend on its place in the batch.  Rows with
+    ``slots[b] < 0`` select 0.  Temperature 0 is :func:`masked_argmax`."""
+    B = logits.shape[0] if logits.dim() == 2 else -1
+    inv_t, seed = _req_sample(slots, positions, B, temperature, seed, "masked_sample")
+    if inv_t == 0.0:
+        return masked_argmax(logits, mask, vocab, out, mask_idx)
+    _req(logits, torch.bfloat16, "masked_sample.logits")
+    B, ld = logits.shape
+    V = vocab or ld
+    W = (V + 31) // 32
+    if V > ld:
+        raise HipOpsError("masked_sample: vocab larger than row")
+    n_masks = 0
+    if mask is not None:
+        _req(mask, torch.int32, "masked_sample.mask")
+        if mask_idx is not None:
+            _req(mask_idx, torch.int32, "masked_sample.mask_idx")
+            if mask.dim() != 2 or mask.shape[1] != W or mask.shape[0] < 1 or mask_idx.numel() != B:
+                raise HipOpsError(f"masked_sample: mask table {tuple(mask.shape)} / mask_idx {mask_idx.numel()} "
+                                  f"do not match B={B}, W={W}")
+            n_masks = mask.shape[0]
+        elif mask.shape != (B, W):
+            raise HipOpsError(f"masked_sample: mask shape {tuple(mask.shape)} != {(B, W)}")
+    elif mask_idx is not None:
+        raise HipOpsError("masked_sample: mask_idx given without a mask table")
+    out = torch.empty((B,), dtype=torch.int32, device=logits.device) if out is None else out
+    _req_out(out, torch.int32, B, "masked_sample.out")
+    _check(lib().dmcp_masked_sample(_ptr(logits), _ptr(mask), _ptr(mask_idx if mask is not None else None), n_masks,
+                                    _ptr(out), B, V, ld, _ptr(slots), _ptr(positions), seed, inv_t, _stream()),
+           "dmcp_masked_sample")
+    return out
+
+
 def pgemm_set_waves(waves: int) -> int:
     """Waves per block of the MX prefill GEMMs: 4 (one per SIMD, 128 x 128
     each) or 8 (two per SIMD, 128 x 64 each).  Returns the previous value."""
@@ -908,6 +985,49 @@ def lm_head_argmax(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_i
         _check(lib().dmcp_lm_head_argmax(_ptr(x[m0:m0 + mc]), _ptr(w), _ptr(masks), _ptr(mask_idx[m0:m0 + mc]),
                                          masks.shape[0], W, _ptr(workspace), _ptr(out[m0:m0 + mc]), mc, V, K,
                                          mparts, _stream()), "dmcp_lm_head_argmax")
+    return out
+
+
+def lm_head_sample(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_idx: torch.Tensor,
+                   out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                   slots: Optional[torch.Tensor] = None, positions: Optional[torch.Tensor] = None,
+                   temperature: float = 0.0, seed: int = 0) -> torch.Tensor:
+    """:func:`lm_head_argmax` at a ``temperature``: the same weight-streaming
+    kernel, tiles, workspace and pair reduction, its epilogue perturbing each
+    allowed bf16 logit / T with the Gumbel noise of :func:`masked_sample`
+    (keys: ``slots`` / ``positions`` int32 [M], ``seed``) -- a sample of
+    softmax(logits / T) over the allowed ids without [M, V] logits.
+    Temperature 0 is :func:`lm_head_argmax`.  Capturable."""
+    M = x.shape[0] if x.dim() == 2 else -1
+    inv_t, seed = _req_sample(slots, positions, M, temperature, seed, "lm_head_sample")
+    if inv_t == 0.0:
+        return lm_head_argmax(x, w, masks, mask_idx, out, workspace)
+    _req(x, torch.bfloat16, "lm_head_sample.x")
+    _req(w, torch.bfloat16, "lm_head_sample.w")
+    _req(masks, torch.int32, "lm_head_sample.masks")
+    _req(mask_idx, torch.int32, "lm_head_sample.mask_idx")
+    M, K = x.shape
+    V = w.shape[0]
+    if w.shape[1] != K or not lm_head_supported(V, K):
+        raise HipOpsError(f"lm_head_sample: x {tuple(x.shape)} / w {tuple(w.shape)} (needs V % 64 == 0, K % 64 == 0)")
+    W = (V + 31) // 32
+    if masks.dim() != 2 or masks.shape[1] != W or mask_idx.numel() != M:
+        raise HipOpsError(f"lm_head_sample: masks {tuple(masks.shape)} / mask_idx {mask_idx.numel()} vs M={M}, W={W}")
+    if out is None:
+        out = torch.empty(M, dtype=torch.int32, device=x.device)
+    _req_out(out, torch.int32, M, "lm_head_sample.out")
+    rows = min(M, WGEMM_MAX_ROWS)
+    if workspace is None:
+        workspace = lm_head_workspace(V, x.device, rows)
+    if workspace.dtype != torch.float32 or workspace.numel() < 2 * (V // 64) * rows:
+        raise HipOpsError("lm_head_sample: workspace too small")
+    for m0 in range(0, M, WGEMM_MAX_ROWS):
+        mc = min(WGEMM_MAX_ROWS, M - m0)
+        mparts = -(-mc // 256)
+        _check(lib().dmcp_lm_head_sample(_ptr(x[m0:m0 + mc]), _ptr(w), _ptr(masks), _ptr(mask_idx[m0:m0 + mc]),
+                                         masks.shape[0], W, _ptr(workspace), _ptr(out[m0:m0 + mc]), mc, V, K,
+                                         mparts, _ptr(slots[m0:m0 + mc]), _ptr(positions[m0:m0 + mc]), seed, inv_t,
+                                         _stream()), "dmcp_lm_head_sample")
     return out
 
 
@@ -1344,6 +1464,38 @@ def tgemm_lm_head_argmax(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, 
     mparts = mparts or tgemm_plan(M, V, K, "argmax")[1]
     _tg(x, w, None, workspace, M, V, K, 1, mparts, 3, 0, masks, mask_idx, masks.shape[0], W, out,
         name="dmcp_tgemm[argmax]")
+    return out
+
+
+def tgemm_lm_head_sample(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_idx: torch.Tensor,
+                         out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                         mparts: int = 0, slots: Optional[torch.Tensor] = None,
+                         positions: Optional[torch.Tensor] = None, temperature: float = 0.0,
+                         seed: int = 0) -> torch.Tensor:
+    """:func:`lm_head_sample` on the large-tile kernel (V % 256 == 0);
+    temperature 0 is :func:`tgemm_lm_head_argmax`."""
+    rows = x.shape[0] if x.dim() == 2 else -1
+    inv_t, seed = _req_sample(slots, positions, rows, temperature, seed, "tgemm_lm_head_sample")
+    if inv_t == 0.0:
+        return tgemm_lm_head_argmax(x, w, masks, mask_idx, out, workspace, mparts)
+    M, K, V = _tgemm_args(x, w, "tgemm_lm_head_sample")
+    _req(masks, torch.int32, "tgemm_lm_head_sample.masks")
+    _req(mask_idx, torch.int32, "tgemm_lm_head_sample.mask_idx")
+    W = (V + 31) // 32
+    if masks.dim() != 2 or masks.shape[1] != W or mask_idx.numel() != M:
+        raise HipOpsError(f"tgemm_lm_head_sample: masks {tuple(masks.shape)} / mask_idx {mask_idx.numel()} vs M={M}")
+    if out is None:
+        out = torch.empty(M, dtype=torch.int32, device=x.device)
+    _req_out(out, torch.int32, M, "tgemm_lm_head_sample.out")
+    need = 2 * (V // 64) * M  # one (max, id) pair per 64-id quarter tile and row
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=x.device)
+    if workspace.dtype != torch.float32 or workspace.numel() < need:
+        raise HipOpsError("tgemm_lm_head_sample: workspace too small")
+    mparts = mparts or tgemm_plan(M, V, K, "argmax")[1]
+    _check(lib().dmcp_tgemm_sample(_ptr(x), _ptr(w), _ptr(workspace), M, V, K, mparts, _ptr(masks), _ptr(mask_idx),
+                                   masks.shape[0], W, _ptr(out), _ptr(slots), _ptr(positions), seed, inv_t,
+                                   _stream()), "dmcp_tgemm_sample")
     return out
 
 

@@ -330,6 +330,109 @@ def lm_head_argmax(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_i
     return masked_argmax(logits, masks, w.shape[0], out, mask_idx)
 
 
+# ---- temperature sampling as a perturbed argmax (Gumbel-max).  The noise is
+# defined in uint32 arithmetic (here: int64 masked to 32 bits), so these
+# functions and the three selection kernels (csrc/dmcp_common.hpp
+# gumbel_score) draw from the same bits:
+#   fmix32(h):  h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16
+#   key(row)     = fmix32(seed ^ fmix32(slot * 0x9E3779B1 + position))
+#   bits(row, v) = fmix32(key(row) + v * 0x9E3779B1)
+#   u = ((bits >> 9) + 0.5) * 2^-23       (exact in fp32, never 0 or 1)
+#   g = -log(-log(u))
+#   score(row, v) = bf16(logit) * fp32(1 / T) + g
+_M32 = 0xFFFFFFFF
+_GOLD = 0x9E3779B1
+
+
+def _fmix32(h: torch.Tensor) -> torch.Tensor:
+    """MurmurHash3's 32-bit finaliser on int64 tensors holding uint32 values."""
+    h = h ^ (h >> 16)
+    h = (h * 0x85EBCA6B) & _M32
+    h = h ^ (h >> 13)
+    h = (h * 0xC2B2AE35) & _M32
+    return h ^ (h >> 16)
+
+
+def gumbel_bits(seed: int, slots: torch.Tensor, positions: torch.Tensor, vocab: int) -> torch.Tensor:
+    """The noise bits [rows, vocab] (uint32 values in int64) of rows keyed by
+    ``slots`` / ``positions`` under ``seed``."""
+    s = slots.to(torch.int64) & _M32          # two's complement, as the kernels' uint32 cast
+    p = positions.to(torch.int64) & _M32
+    key = _fmix32((int(seed) & _M32) ^ _fmix32((s * _GOLD + p) & _M32))
+    v = torch.arange(vocab, dtype=torch.int64, device=slots.device)
+    return _fmix32((key[:, None] + ((v * _GOLD) & _M32)[None, :]) & _M32)
+
+
+def gumbel_noise(seed: int, slots: torch.Tensor, positions: torch.Tensor, vocab: int,
+                 dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Standard Gumbel variates [rows, vocab] in ``dtype`` (fp32 or fp64) from :func:`gumbel_bits`."""
+    bits = gumbel_bits(seed, slots, positions, vocab)
+    u = ((bits >> 9) * 2 + 1).to(dtype) * 2.0 ** -24  # ((bits >> 9) + 0.5) * 2^-23, exact in fp32
+    return -torch.log(-torch.log(u))
+
+
+def _sample_args(B: int, slots, positions, temperature) -> float:
+    t = float(temperature)
+    if not math.isfinite(t) or t < 0:
+        raise ValueError(f"masked_sample: temperature must be finite and >= 0, got {temperature!r}")
+    for key, which in ((slots, "slots"), (positions, "positions")):
+        if not isinstance(key, torch.Tensor) or key.dtype != torch.int32 or key.numel() != B:
+            raise ValueError(f"masked_sample: {which} must be int32 [{B}] (they key each row's noise)")
+    return t
+
+
+def sample_scores(logits: torch.Tensor, mask: Optional[torch.Tensor], vocab: Optional[int],
+                  mask_idx: Optional[torch.Tensor], slots: torch.Tensor, positions: torch.Tensor,
+                  temperature: float, seed: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """The scores [B, V] whose row-wise argmax :func:`masked_sample` returns
+    (temperature > 0): bf16(logit) * fp32(1 / T) + Gumbel noise in ``dtype``
+    (fp32 as the kernels compute, fp64 for tests), -inf for the ids the row's
+    mask excludes and for every id of a row whose slot is < 0."""
+    B, ld = logits.shape
+    t = _sample_args(B, slots, positions, temperature)
+    if t == 0:
+        raise ValueError("sample_scores: temperature must be > 0")
+    V = vocab or ld
+    inv_t = float(torch.tensor(1.0 / t, dtype=torch.float32))
+    x = logits[:, :V].to(torch.bfloat16).to(dtype) * inv_t + gumbel_noise(seed, slots, positions, V, dtype)
+    if mask is not None and mask_idx is not None:
+        mask = mask[mask_idx.long().clamp(0, mask.shape[0] - 1)]
+    if mask is not None:
+        idx = torch.arange(V, device=logits.device)
+        words = mask.to(torch.int64)[:, idx // 32]
+        bits = (words >> (idx % 32)) & 1
+        x[bits == 0] = float("-inf")
+    x[slots.long() < 0] = float("-inf")
+    return x
+
+
+def masked_sample(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, vocab: Optional[int] = None,
+                  out: Optional[torch.Tensor] = None, mask_idx: Optional[torch.Tensor] = None,
+                  slots: Optional[torch.Tensor] = None, positions: Optional[torch.Tensor] = None,
+                  temperature: float = 0.0, seed: int = 0) -> torch.Tensor:
+    """:func:`masked_argmax` at a temperature: the allowed id with the highest
+    bf16(logit) / T + Gumbel noise, an exact sample of softmax(logits / T) over
+    the allowed ids; the lowest id among ties, 0 when nothing is allowed or the
+    row's slot is < 0 (padding).  Temperature 0 is :func:`masked_argmax`."""
+    if _sample_args(logits.shape[0], slots, positions, temperature) == 0:
+        return masked_argmax(logits, mask, vocab, out, mask_idx)
+    x = sample_scores(logits, mask, vocab, mask_idx, slots, positions, temperature, seed)
+    ids = torch.argmax(x, dim=-1).to(torch.int32)  # first index among ties; 0 for an all -inf row
+    if out is not None:
+        out.copy_(ids)
+        return out
+    return ids
+
+
+def lm_head_sample(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_idx: torch.Tensor,
+                   out: Optional[torch.Tensor] = None, workspace=None, slots: Optional[torch.Tensor] = None,
+                   positions: Optional[torch.Tensor] = None, temperature: float = 0.0,
+                   seed: int = 0) -> torch.Tensor:
+    """The fused LM head + sampling's definition: F.linear then masked_sample."""
+    logits = (x.float() @ w.float().t()).to(torch.bfloat16)
+    return masked_sample(logits, masks, w.shape[0], out, mask_idx, slots, positions, temperature, seed)
+
+
 def embedding(table: torch.Tensor, ids: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     y = table[ids.long().clamp(0, table.shape[0] - 1)]
     if out is not None:

@@ -1,0 +1,96 @@
+"""The cost of temperature sampling in the selection kernels: each op at
+temperature 0 (the greedy kernel) and at --temperature, alternated --rounds
+times on one device, every timing a captured graph of --reps back-to-back
+calls (no Python wrapper cost).  One JSON line per op and shape.
+
+  python scripts/bench_sampling.py [--rows 512 610] [--vocab 128256] [--hidden 2048]
+
+Rows <= 512 time lm_head_sample (wgemm.hip), rows above it tgemm_lm_head_sample
+(tgemm.hip); --masked-rows time masked_sample over [rows, vocab] bf16 logits.
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _timed(fn, reps):
+    import torch
+    for _ in range(3):
+        fn()
+    graph = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(graph, stream=side):
+            for _ in range(reps):
+                fn()
+    torch.cuda.current_stream().wait_stream(side)
+    graph.replay()
+    torch.cuda.synchronize()
+
+    def run():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        graph.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / reps
+    return run
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, nargs="+", default=[512, 610])
+    ap.add_argument("--masked-rows", type=int, nargs="*", default=[16, 64])
+    ap.add_argument("--vocab", type=int, default=128256)
+    ap.add_argument("--hidden", type=int, default=2048)
+    ap.add_argument("--temperature", type=float, default=0.7)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=5)
+    args = ap.parse_args()
+    import torch
+    from dmcp.ops import hip
+    V, K, T = args.vocab, args.hidden, args.temperature
+    W = (V + 31) // 32
+    g = torch.Generator(device="cuda").manual_seed(0)
+    masks = torch.randint(-2 ** 31, 2 ** 31 - 1, (8, W), device="cuda", dtype=torch.int32, generator=g)
+    w = (torch.randn(V, K, device="cuda", generator=g) * 0.02).to(torch.bfloat16)
+
+    def report(name, M, make):
+        midx = torch.randint(0, 8, (M,), device="cuda", dtype=torch.int32, generator=g)
+        slots = torch.randint(0, 768, (M,), device="cuda", dtype=torch.int32, generator=g)
+        pos = torch.randint(0, 8192, (M,), device="cuda", dtype=torch.int32, generator=g)
+        runs = {t: _timed(make(midx, slots, pos, t), args.reps) for t in (0.0, T)}
+        us = {t: [] for t in runs}
+        for _ in range(args.rounds):  # alternated: drift of the device shows in both columns
+            for t, run in runs.items():
+                us[t].append(round(run(), 2))
+        med = {t: sorted(v)[len(v) // 2] for t, v in us.items()}
+        print(json.dumps({"bench": name, "rows": M, "vocab": V, "hidden": K, "temperature": T,
+                          "greedy_us": us[0.0], "sampled_us": us[T], "greedy_median_us": med[0.0],
+                          "sampled_median_us": med[T], "added_us": round(med[T] - med[0.0], 2),
+                          "greedy_spread_us": round(max(us[0.0]) - min(us[0.0]), 2)}), flush=True)
+
+    for M in args.rows:
+        x = (torch.randn(M, K, device="cuda", generator=g) * 0.5).to(torch.bfloat16)
+        out = torch.empty(M, dtype=torch.int32, device="cuda")
+        if M <= hip.WGEMM_MAX_ROWS:
+            ws = hip.lm_head_workspace(V, "cuda", M)
+            report("lm_head_sample", M, lambda mi, s, p, t: lambda: hip.lm_head_sample(
+                x, w, masks, mi, out, ws, s, p, t, 1))
+        else:
+            ws = torch.empty(2 * (V // 64) * M, dtype=torch.float32, device="cuda")
+            report("tgemm_lm_head_sample", M, lambda mi, s, p, t: lambda: hip.tgemm_lm_head_sample(
+                x, w, masks, mi, out, ws, 0, s, p, t, 1))
+    for B in args.masked_rows:
+        logits = torch.randn(B, V, device="cuda", generator=g).to(torch.bfloat16)
+        out = torch.empty(B, dtype=torch.int32, device="cuda")
+        report("masked_sample", B, lambda mi, s, p, t: lambda: hip.masked_sample(
+            logits, masks, V, out, mi, s, p, t, 1))
+
+
+if __name__ == "__main__":
+    main()

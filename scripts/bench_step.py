@@ -52,6 +52,9 @@ def main(argv=None) -> int:
                     help="per-sequence own length uniform in ctx x [1 - j, 1 + j] (the engine's mix of progress)")
     ap.add_argument("--adjacent", action="store_true",
                     help="jump rows next to their sequence's row (the engine's row order) instead of at the end")
+    ap.add_argument("--temperature", type=float, default=0.0,
+                    help="selection temperature of the step (0 = greedy; above it the sampling kernels)")
+    ap.add_argument("--seed", type=int, default=0, help="sampling seed")
     a = ap.parse_args(argv)
 
     from dmcp.enrich.local import LocalEngine
@@ -75,7 +78,7 @@ def main(argv=None) -> int:
     if a.tghead == 0:
         model.tg_head = False
     hip.wgemm_set_aux(a.wgemm_aux)
-    eng = LocalEngine(model)
+    eng = LocalEngine(model, **({"temperature": a.temperature, "seed": a.seed} if a.temperature > 0 else {}))
     g = torch.Generator().manual_seed(0)
     if a.prefix:
         model.set_prefix(torch.randint(0, 256, (a.prefix,), generator=g).tolist())
@@ -125,7 +128,8 @@ def main(argv=None) -> int:
     loop_ms = (time.perf_counter() - t0) / a.iters * 1e3
     kv_bytes = 2 * cfg.layers * cfg.n_kv_heads * cfg.head_dim * cfg.kv_elem_bytes * (sum(ctxs) + a.batch + a.prefix)
     w_bytes = 2 * (cfg.param_count() - cfg.vocab_size * cfg.hidden)
-    print(json.dumps({"bench": "decode_step", "preset": a.preset, "kv_dtype": a.kv_dtype, "decode_dtype": a.decode_dtype, "rows": n, "batch": a.batch, "prefix": a.prefix,
+    print(json.dumps({"bench": "decode_step", "preset": a.preset, "kv_dtype": a.kv_dtype, "decode_dtype": a.decode_dtype, "temperature": a.temperature, "rows": n,
+                      "graph_kernels": graphs.graphs[graphs.bucket_for(n)].kernels, "batch": a.batch, "prefix": a.prefix,
                       "ctx": a.ctx, "jitter": a.jitter, "adjacent": a.adjacent, "fused": bool(getattr(model, "use_fused", False)),
                       "tgemm": bool(getattr(model, "use_tgemm", False)),
                       "tg_head": bool(getattr(model, "tg_head", False)), "wgemm_aux": a.wgemm_aux,
