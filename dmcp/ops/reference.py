@@ -32,10 +32,12 @@ FP8_MAX = 448.0
 
 
 def kv_float(t: torch.Tensor) -> torch.Tensor:
-    """Cache values as fp32 (bf16 caches, or fp8 e4m3 caches stored as uint8)."""
+    """Cache values as fp32 (bf16 caches, or fp8 e4m3 caches stored as uint8).
+    An fp64 tensor stays fp64: the attention references then run in fp64
+    (tests/needles.py decodes the caches and passes them that way)."""
     if t.dtype == torch.uint8:
         return t.view(torch.float8_e4m3fn).float()
-    return t.float()
+    return t if t.dtype == torch.float64 else t.float()
 
 
 def kv_encode(x: torch.Tensor, cache_dtype: torch.dtype) -> torch.Tensor:
@@ -226,7 +228,7 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     S, Hkv, MAXS, _ = k_cache.shape
     G = Hq // Hkv
     P = int(prefix.length.reshape(-1)[0]) if prefix is not None else 0
-    res = torch.zeros((B, Hq, D), dtype=torch.float32, device=q.device)
+    res = torch.zeros((B, Hq, D), dtype=kv_float(q).dtype, device=q.device)
     for b in range(B):
         s, L = int(slot[b]), min(int(seq_len[b]), MAXS)
         if not (0 <= s < S) or L <= 0:
@@ -241,7 +243,7 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
         if P > 0 and (prefix.rows is None or int(prefix.rows[b]) != 0):  # the first P keys: the shared prefix
             k = torch.cat([kv_float(prefix.k[:, :P]), k[:, P:]], dim=1)
             v = torch.cat([kv_float(prefix.v[:, :P]), v[:, P:]], dim=1)
-        qb = q[b].float().view(Hkv, G, D)
+        qb = kv_float(q[b]).view(Hkv, G, D)
         att = torch.einsum("hgd,hld->hgl", qb, k) * scale
         p = torch.softmax(att, dim=-1)
         res[b] = torch.einsum("hgl,hld->hgd", p, v).reshape(Hq, D)
@@ -267,7 +269,7 @@ def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     if prefix_len > 0:
         k = torch.cat([kv_float(k_cache[prefix_slot, :, :prefix_len]), k[:, prefix_len:]], dim=1)
         v = torch.cat([kv_float(v_cache[prefix_slot, :, :prefix_len]), v[:, prefix_len:]], dim=1)
-    qf = q.float().view(T, Hkv, G, D)
+    qf = kv_float(q).view(T, Hkv, G, D)
     att = torch.einsum("thgd,hld->hgtl", qf, k) * scale  # [Hkv, G, T, L]
     pos = torch.arange(start, L, device=q.device)[:, None]
     att = att.masked_fill(torch.arange(L, device=q.device)[None, :] > pos, float("-inf"))
