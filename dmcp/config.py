@@ -83,6 +83,14 @@ class Config:
     # (dmcp/ops/reference.py gumbel_noise).  Every worker uses the same seed.
     local_llm_temperature: float = 0.0
     local_llm_seed: int = 0
+    # truncation of those draws (ignored at temperature 0): the top_k largest
+    # logits (0 = off), then the smallest set of values whose probability
+    # reaches top_p (1.0 = off), and the ids with at least min_p of the most
+    # likely id's probability (0.0 = off) -- dmcp/ops/reference.py
+    # truncation_threshold.  Checked when the engine is built.
+    local_llm_top_k: int = 0
+    local_llm_top_p: float = 1.0
+    local_llm_min_p: float = 0.0
     local_llm_devices: str = "all"
     # "process": one worker process per GPU, started before this process
     # touches HIP (the service default); "inline": engines in this process
@@ -162,6 +170,9 @@ class Config:
             "LOCAL_LLM_MAX_STEPS": "local_llm_max_steps",
             "LOCAL_LLM_TEMPERATURE": "local_llm_temperature",
             "LOCAL_LLM_SEED": "local_llm_seed",
+            "LOCAL_LLM_TOP_K": "local_llm_top_k",
+            "LOCAL_LLM_TOP_P": "local_llm_top_p",
+            "LOCAL_LLM_MIN_P": "local_llm_min_p",
             "LOCAL_LLM_DEVICES": "local_llm_devices",
             "LOCAL_LLM_WORKERS": "local_llm_workers",
             "LOCAL_LLM_MAX_BATCH": "local_llm_max_batch",

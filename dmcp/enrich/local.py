@@ -53,6 +53,7 @@ from typing import Any, Deque, Dict, Iterable, Iterator, List, Optional, Sequenc
 import torch
 
 from ..models.llm import LocalLM, LMConfig, DecodeGraphs, preset
+from ..ops.reference import truncation_args
 from .backend import SYNTHETIC_PREFIX, EnrichmentBackend, build_enrichment_prompt
 from .jsonfix import parse_enrichment_response
 from .tokenizer import ByteTokenizer
@@ -513,7 +514,8 @@ class LocalEngine:
                  max_new_tokens: Optional[int] = None, native_grammar: Optional[bool] = None,
                  fork_methods: bool = True, fork_max_context: int = 0,
                  reply_shape: Optional[ReplyShape] = None, type_choice: Optional[bool] = None,
-                 precapture: Optional[bool] = None, temperature: float = 0.0, seed: int = 0) -> None:
+                 precapture: Optional[bool] = None, temperature: float = 0.0, seed: int = 0,
+                 top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0) -> None:
         self.model = model
         # temperature 0 (the default) is the greedy selection, unchanged; above
         # it every selected token -- the decode steps' and the first one after
@@ -528,6 +530,19 @@ class LocalEngine:
         self.seed = int(seed)
         self._sample = (temperature, self.seed & 0xFFFFFFFF) if temperature > 0 else None
         self._sample_kw = {"sample": self._sample} if self._sample is not None else {}
+        # top-k / top-p / min-p truncation of those draws (0 / 1.0 / 0.0: off;
+        # dmcp.ops.truncated_sample, the definitions in dmcp/ops/reference.py).
+        # Ignored at temperature 0: the greedy id survives every truncation.
+        # With a filter on, a step writes its logits (a buffer the model
+        # allocates once, here) and selects with the row-wide kernel instead
+        # of the fused head; with all three off every path is the untruncated one.
+        self.top_k, self.top_p, self.min_p = truncation_args(top_k, top_p, min_p)
+        self._truncate = ((self.top_k, self.top_p, self.min_p)
+                          if self._sample is not None and (self.top_k, self.top_p, self.min_p) != (0, 1.0, 0.0)
+                          else None)
+        if self._truncate is not None:
+            self._sample_kw["truncate"] = self._truncate
+            model.reserve_truncation_logits()
         self.tok = tokenizer if tokenizer is not None else ByteTokenizer(model.cfg.vocab_size)
         self._tb = self.tok.token_bytes
         self._quote = self.tok.quote
@@ -1003,9 +1018,12 @@ class LocalEngine:
                 if dev.type == "cuda":
                     keys = keys.pin_memory()
                 keys = keys.to(dev, non_blocking=True)
-                ids = ops.masked_sample(rows.contiguous(), self.masks, vocab=self.cfg.vocab_size, mask_idx=midx,
-                                        slots=keys[0], positions=keys[1], temperature=self._sample[0],
-                                        seed=self._sample[1])
+                cut = ({} if self._truncate is None else
+                       {"top_k": self._truncate[0], "top_p": self._truncate[1], "min_p": self._truncate[2]})
+                select = ops.masked_sample if self._truncate is None else ops.truncated_sample
+                ids = select(rows.contiguous(), self.masks, vocab=self.cfg.vocab_size, mask_idx=midx,
+                             slots=keys[0], positions=keys[1], temperature=self._sample[0],
+                             seed=self._sample[1], **cut)
             else:
                 ids = ops.masked_argmax(rows.contiguous(), self.masks, vocab=self.cfg.vocab_size, mask_idx=midx)
             host = torch.empty(len(need), dtype=torch.int32, pin_memory=dev.type == "cuda")

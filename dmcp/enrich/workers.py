@@ -671,7 +671,10 @@ def engine_spec(cfg) -> dict:
                             "step": int(getattr(cfg, "local_llm_step_max_bytes", 0)),
                             "max_steps": int(getattr(cfg, "local_llm_max_steps", 0))},
             "temperature": float(getattr(cfg, "local_llm_temperature", 0.0)),
-            "seed": int(getattr(cfg, "local_llm_seed", 0))}
+            "seed": int(getattr(cfg, "local_llm_seed", 0)),
+            "top_k": int(getattr(cfg, "local_llm_top_k", 0)),
+            "top_p": float(getattr(cfg, "local_llm_top_p", 1.0)),
+            "min_p": float(getattr(cfg, "local_llm_min_p", 0.0))}
 
 
 # ------------------------------------------------------------------ child

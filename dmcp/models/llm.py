@@ -58,6 +58,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import ops
+from ..ops.reference import truncation_args
 
 BYTE_VOCAB = 256
 BOS, EOS, PAD = 256, 257, 258
@@ -382,6 +383,16 @@ def _kv_bf16(t: torch.Tensor) -> torch.Tensor:
     return ops.reference.kv_float(t).to(torch.bfloat16) if t.dtype == torch.uint8 else t
 
 
+def _truncation(sample: Optional[tuple], truncate: Optional[tuple]) -> Optional[tuple]:
+    """(top_k, top_p, min_p), validated, of a sampled selection with a filter
+    on; None when the selection is greedy or every filter is off (those paths
+    are the untruncated ones, unchanged)."""
+    if truncate is None or sample is None or not sample[0] > 0:
+        return None
+    cut = truncation_args(*truncate)
+    return None if cut == (0, 1.0, 0.0) else cut
+
+
 class LocalLM:
     """Weights + KV cache + forward passes (prefill / extend / batched decode).
 
@@ -508,6 +519,12 @@ class LocalLM:
                         and self.max_rows >= self.TGEMM_HEAD_MIN_ROWS and self.max_rows <= ops.TGEMM_MAX_ROWS)
         self.tg_head_ws = (torch.empty(2 * (c.vocab_size // 64) * self.max_rows, dtype=torch.float32,
                                        device=self.device) if self.tg_head else None)
+        # the [max_rows, vocab] bf16 logits of steps that sample under a top-k /
+        # top-p / min-p truncation (a truncation needs the whole row before the
+        # draw, so those steps leave the fused head): allocated once, by
+        # reserve_truncation_logits(), only when a filter is configured
+        # (263 MB at 1,024 x 128,256)
+        self.trunc_logits: Optional[torch.Tensor] = None
         # fp8 prefill: e4m3 copies of the four projections (per-row scales),
         # quantised once; the batched prefill then runs on csrc/pgemm.hip
         # (the CPU references take any dims the 32-element blocks divide)
@@ -1128,16 +1145,47 @@ class LocalLM:
         """``slots`` own all their keys again (a freed or newly admitted slot)."""
         self._fork_set([(int(x), int(x), 0) for x in slots])
 
+    def reserve_truncation_logits(self) -> Optional[torch.Tensor]:
+        """The logits buffer of truncated sampling past the small-step row
+        count (GPU; None elsewhere), allocated on the first call: an engine
+        with a filter configured calls it when it is built, before any graph
+        is captured."""
+        if self.trunc_logits is None and self.fused_head:
+            self.trunc_logits = torch.empty((self.max_rows, self.cfg.vocab_size), dtype=self.dtype,
+                                            device=self.device)
+        return self.trunc_logits
+
+    def _head_into(self, h: torch.Tensor, buf: torch.Tensor) -> torch.Tensor:
+        """The LM head's logits of a decode step written to ``buf[:rows]``:
+        the large-tile GEMM from TGEMM_HEAD_MIN_ROWS rows where the fused
+        head would use it, the weight-streaming GEMM below (as :meth:`_head`),
+        hipBLASLt only off their shape contracts."""
+        B = h.shape[0]
+        out = buf[:B]
+        if self.tg_head and B >= self.TGEMM_HEAD_MIN_ROWS:
+            return ops.tgemm(h, self.w["lm_head"], out=out)
+        if self.use_wgemm and B <= ops.WGEMM_MAX_ROWS and self.cfg.vocab_size % 64 == 0:
+            return ops.wgemm(h.contiguous(), self.w["lm_head"], out=out)
+        return torch.matmul(h, self.w["lm_head"].t(), out=out)
+
     def decode_select(self, tokens: torch.Tensor, slots: torch.Tensor, positions: torch.Tensor,
-                      masks: torch.Tensor, mask_idx: torch.Tensor, sample: Optional[tuple] = None) -> tuple:
+                      masks: torch.Tensor, mask_idx: torch.Tensor, sample: Optional[tuple] = None,
+                      truncate: Optional[tuple] = None) -> tuple:
         """:meth:`decode` + selection under a per-row grammar mask
         (``masks`` [M, ceil(V/32)] bitsets, ``mask_idx`` int32 [B]): greedy,
         or with ``sample`` = (temperature, seed) a draw from softmax(logits /
         temperature) over the allowed ids, keyed by the row's slot and
-        position (:func:`dmcp.ops.masked_sample`; temperature 0 is greedy).
+        position (:func:`dmcp.ops.masked_sample`; temperature 0 is greedy);
+        ``truncate`` = (top_k, top_p, min_p) restricts that draw
+        (:func:`dmcp.ops.truncated_sample`; ignored when greedy).
         Returns (logits, ids int32 [B]); capturable."""
         logits = self.decode(tokens, slots, positions)
-        if sample is not None:
+        cut = _truncation(sample, truncate)
+        if cut is not None:
+            ids = ops.truncated_sample(logits, masks, vocab=self.cfg.vocab_size, mask_idx=mask_idx, slots=slots,
+                                       positions=positions, temperature=sample[0], seed=sample[1], top_k=cut[0],
+                                       top_p=cut[1], min_p=cut[2])
+        elif sample is not None:
             ids = ops.masked_sample(logits, masks, vocab=self.cfg.vocab_size, mask_idx=mask_idx, slots=slots,
                                     positions=positions, temperature=sample[0], seed=sample[1])
         else:
@@ -1148,7 +1196,7 @@ class LocalLM:
                              slots: torch.Tensor, positions: torch.Tensor, masks: torch.Tensor,
                              mask_idx: torch.Tensor, mask_alt: Optional[torch.Tensor] = None,
                              alt_token: int = -1, prefix_rows: Optional[torch.Tensor] = None,
-                             sample: Optional[tuple] = None) -> tuple:
+                             sample: Optional[tuple] = None, truncate: Optional[tuple] = None) -> tuple:
         """:meth:`decode_select` whose input token of row r is ``last_ids[src[r]]``
         where ``src[r] >= 0`` (the previous step's selection, still on the
         device) and ``tokens[r]`` otherwise; the step's own selections are
@@ -1157,15 +1205,28 @@ class LocalLM:
         ``mask_alt`` / ``alt_token`` / ``prefix_rows``: see :meth:`decode`.
         ``sample`` = (temperature, seed): every path samples instead (the
         same tiles and launches: the selection kernels' sampling variants).
-        Capturable."""
+        ``truncate`` = (top_k, top_p, min_p) with a filter on (and a
+        temperature above 0): the fused head is not taken -- the step writes
+        its bf16 logits with the plain GEMM (:meth:`_head_into`, into the
+        buffer of :meth:`reserve_truncation_logits`) and selects with
+        :func:`dmcp.ops.truncated_sample`, as many kernels as the fused head
+        and its pair reduction; the logits are returned.  Capturable."""
         B = tokens.shape[0]
         keys = {} if sample is None else {"slots": slots, "positions": positions, "temperature": sample[0],
                                           "seed": sample[1]}
+        cut = _truncation(sample, truncate)
+        if cut is not None:
+            keys.update(top_k=cut[0], top_p=cut[1], min_p=cut[2])
         if self.fused_head and not (self.use_fused and B <= self.fused_max_rows):
-            # the LM head + grammar-masked selection in one weight-streaming
-            # kernel: no [B, vocab] logits (returned as None)
             h = self._decode_trunk(tokens, slots, positions, src, last_ids, mask_idx, mask_alt, alt_token,
                                    prefix_rows)
+            if cut is not None:
+                logits = self._head_into(h, self.reserve_truncation_logits())
+                ids = ops.truncated_sample(logits, masks, vocab=self.cfg.vocab_size, mask_idx=mask_idx,
+                                           out=last_ids[:B], **keys)
+                return logits, ids
+            # the LM head + grammar-masked selection in one weight-streaming
+            # kernel: no [B, vocab] logits (returned as None)
             if self.tg_head and B >= self.TGEMM_HEAD_MIN_ROWS:
                 head = ops.tgemm_lm_head_argmax if sample is None else ops.tgemm_lm_head_sample
                 ids = head(h, self.w["lm_head"], masks, mask_idx, out=last_ids[:B], workspace=self.tg_head_ws, **keys)
@@ -1175,7 +1236,8 @@ class LocalLM:
             return None, ids
         logits = self.decode(tokens, slots, positions, src=src, last_ids=last_ids, mask_idx=mask_idx,
                              mask_alt=mask_alt, alt_token=alt_token, prefix_rows=prefix_rows)
-        select = ops.masked_argmax if sample is None else ops.masked_sample
+        select = (ops.masked_argmax if sample is None else ops.masked_sample if cut is None
+                  else ops.truncated_sample)
         ids = select(logits, masks, vocab=self.cfg.vocab_size, mask_idx=mask_idx, out=last_ids[:B], **keys)
         return logits, ids
 
@@ -1291,13 +1353,18 @@ class DecodeGraphs:
     def __init__(self, model: LocalLM, masks: torch.Tensor,
                  buckets: Sequence[int] = (1, 2, 4, 8, 16, 32, 64, 96, 128, 192, 256, 320, 384, 448, 512, 640,
                                           768, 896, 1024), alt_token: int = -1,
-                 sample: Optional[tuple] = None) -> None:
+                 sample: Optional[tuple] = None, truncate: Optional[tuple] = None) -> None:
         self.model = model
         self.masks = masks
         self.alt_token = int(alt_token)
         # (temperature, seed) of a sampling engine, fixed for its lifetime: a
         # constant of the captured selection kernels (None: greedy)
         self.sample = sample
+        # (top_k, top_p, min_p) of that engine (None: no truncation): the
+        # captured step then writes logits and selects with truncated_sample
+        self.truncate = truncate
+        if _truncation(sample, truncate) is not None:
+            model.reserve_truncation_logits()  # before any capture
         self.timing = {"sync_s": 0.0, "replay_s": 0.0}  # host time inside run(): staging wait, H2D + launch
         # device witness: graph replays and the kernel nodes they launched
         self.counts = {"graph_replays": 0, "graph_kernels": 0}
@@ -1339,14 +1406,14 @@ class DecodeGraphs:
         with torch.cuda.stream(s):
             for _ in range(2):  # warm up hipBLASLt heuristics / allocator outside capture
                 m.decode_select_gather(inp[0], inp[4], scratch, inp[1], inp[2], self.masks, inp[3], inp[5],
-                                       self.alt_token, inp[6], self.sample)
+                                       self.alt_token, inp[6], self.sample, self.truncate)
         torch.cuda.current_stream().wait_stream(s)
         # keep_graph: the hipGraph_t stays queryable after capture (the kernel
         # node count of the witness); instantiated explicitly right after
         g = torch.cuda.CUDAGraph(keep_graph=True)
         with torch.cuda.graph(g):
             logits, ids = m.decode_select_gather(inp[0], inp[4], self.last_ids, inp[1], inp[2], self.masks, inp[3],
-                                                 inp[5], self.alt_token, inp[6], self.sample)
+                                                 inp[5], self.alt_token, inp[6], self.sample, self.truncate)
         bucket = _Bucket(g, inp, logits, ids, b)
         g.instantiate()
         self.graphs[b] = bucket
@@ -1373,7 +1440,7 @@ class DecodeGraphs:
                               list(prefix_rows)], dtype=torch.int32, device=m.device)
             return m.decode_select_gather(t[0].contiguous(), t[4].contiguous(), self.last_ids, t[1].contiguous(),
                                           t[2].contiguous(), self.masks, t[3].contiguous(), t[5].contiguous(),
-                                          self.alt_token, t[6].contiguous(), self.sample)
+                                          self.alt_token, t[6].contiguous(), self.sample, self.truncate)
         b = self.bucket_for(n)
         if b not in self.graphs:
             self._capture(b)

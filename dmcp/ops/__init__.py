@@ -18,8 +18,8 @@ from .hip import (FUSED_MAX_ROWS, PREFIX_MFMA_MAX_SPLITS, WGEMM_MAX_ROWS, decode
                   prefill_supported, wgemm_resid_norm, wgemm_rope_kv, wgemm_swiglu, wgemm_workspace)
 from .hip import (PGEMM_TILE_N, WMX_MAX_ROWS, pgemm_supported, wgemm_mx_resid_norm, wgemm_mx_rope_kv,  # noqa: F401
                   wgemm_mx_swiglu, wmx_plan)
-from .hip import (TGEMM_MAX_ROWS, tgemm_lm_head_argmax, tgemm_lm_head_sample, tgemm_resid_norm,  # noqa: F401
-                  tgemm_rope_kv, tgemm_swiglu, wgemm)
+from .hip import (TGEMM_MAX_ROWS, tgemm, tgemm_lm_head_argmax, tgemm_lm_head_sample,  # noqa: F401
+                  tgemm_resid_norm, tgemm_rope_kv, tgemm_swiglu, wgemm)
 from .reference import SharedPrefix, mx_dequant, quantize_weight, rope_tables, weight_dequant  # noqa: F401
 
 
@@ -45,12 +45,14 @@ def _by_device(name: str):
 
 
 # ops with an fp32 CPU reference: norms, RoPE + KV append, prefill attention,
-# SwiGLU, selection (greedy, and sampled at a temperature), embedding, the
+# SwiGLU, selection (greedy, sampled at a temperature, and sampled under
+# top-k / top-p / min-p truncation), embedding, the
 # decode step's input gather + first norm, the MXFP8 prefill path
 # (csrc/pgemm.hip), and the three fused QKV projections (their references
 # define where the optional bias and QK-norm enter)
 DEVICE_OPS = ("add_rmsnorm", "rope_kv", "prefill_attention", "prefill_attention_varlen", "silu_mul",
-              "masked_argmax", "lm_head_argmax", "masked_sample", "lm_head_sample", "embedding", "decode_embed_norm",
+              "masked_argmax", "lm_head_argmax", "masked_sample", "lm_head_sample", "truncated_sample", "embedding",
+              "decode_embed_norm",
               "mx_quant", "rmsnorm_mx", "pgemm", "pgemm_resid", "pgemm_swiglu", "pgemm_qkv", "fused_rope_kv",
               "wgemm_rope_kv", "tgemm_rope_kv")
 for _name in DEVICE_OPS:

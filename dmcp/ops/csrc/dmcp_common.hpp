@@ -257,6 +257,11 @@ inline sample_keys_t<SAMPLE> pick_keys(const SampleKeys& sk) {
     else return {};
 }
 
+// the selection kernels' merge rule: the highest value, the lowest id among ties
+__device__ __forceinline__ void argmax_take(float x, int v, float& best, int& bi) {
+    if (x > best || (x == best && v < bi)) { best = x; bi = v; }
+}
+
 // The LM head's per-row selection from per-tile (max, id) pairs (wgemm.hip /
 // tgemm.hip MODE_ARGMAX write best[tile * M + row]): the highest value, the
 // lowest id among ties; 0 when the mask allowed nothing (as masked_argmax).

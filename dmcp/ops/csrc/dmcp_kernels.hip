@@ -315,10 +315,6 @@ __global__ __launch_bounds__(kBlock) void silu_mul_kernel(const uint16_t* __rest
 //    selects the grammar state per row without an index_select; without it,
 //    mask row b.  Ties resolve to the smallest index.
 // --------------------------------------------------------------------------
-__device__ __forceinline__ void argmax_take(float x, int v, float& best, int& bi) {
-    if (x > best || (x == best && v < bi)) { best = x; bi = v; }
-}
-
 // One 1,024-thread block per row.  Whole 8-id chunks are read as one 16-B
 // load each with the chunk's 8 mask bits (one byte of a mask word), MA_U
 // chunks per thread issued before any is compared (indices clamped, the

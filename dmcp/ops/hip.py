@@ -21,6 +21,7 @@ from typing import Callable, Optional
 import numpy as np
 import torch
 
+from . import reference
 from .build import TARGET, build
 
 _lib = None
@@ -101,6 +102,9 @@ def lib() -> ctypes.CDLL:
             "dmcp_lm_head_sample": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _u, _f, _vp],
                                     _i),
             "dmcp_tgemm_sample": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _u, _f, _vp], _i),
+            # dmcp_masked_sample's list + top_k, top_p, fp32(log(min_p)), stats (ahead of the stream)
+            "dmcp_truncated_sample": ([_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _u, _f, _i, _f, _f, _vp, _vp],
+                                      _i),
         }
         for name, (args, res) in sigs.items():
             try:
@@ -652,6 +656,61 @@ def masked_sample(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, voc
     _check(lib().dmcp_masked_sample(_ptr(logits), _ptr(mask), _ptr(mask_idx if mask is not None else None), n_masks,
                                     _ptr(out), B, V, ld, _ptr(slots), _ptr(positions), seed, inv_t, _stream()),
            "dmcp_masked_sample")
+    return out
+
+
+def truncated_sample(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, vocab: Optional[int] = None,
+                     out: Optional[torch.Tensor] = None, mask_idx: Optional[torch.Tensor] = None,
+                     slots: Optional[torch.Tensor] = None, positions: Optional[torch.Tensor] = None,
+                     temperature: float = 0.0, seed: int = 0, top_k: int = 0, top_p: float = 1.0,
+                     min_p: float = 0.0, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`masked_sample` under top-k / top-p / min-p truncation
+    (csrc/truncate.hip; the definitions: :func:`dmcp.ops.reference.truncation_threshold`):
+    ids[b] is a sample of the renormalised softmax(logits[b] / temperature)
+    over the allowed ids whose bf16 value is >= the row's threshold tau --
+    the ``top_k`` largest values (0 = off), then the smallest set of value
+    levels whose mass reaches ``top_p`` (1 = off), and the values within
+    ``min_p`` of the maximum's probability (0 = off); ties at a threshold are
+    kept together.  Same noise, keys and tie rule as :func:`masked_sample`,
+    which it equals with every filter off.  ``stats`` (int32 [B, 2]) receives
+    the bf16 bits of tau (0xFF80 = -inf when no filter cuts) and the kept
+    count.  Temperature 0 is :func:`masked_argmax` (``stats`` is not
+    written).  One launch, no allocation beyond ``out``; capturable."""
+    B = logits.shape[0] if logits.dim() == 2 else -1
+    inv_t, seed = _req_sample(slots, positions, B, temperature, seed, "truncated_sample")
+    try:
+        top_k, top_p, min_p = reference.truncation_args(top_k, top_p, min_p)
+    except ValueError as e:
+        raise HipOpsError(f"truncated_sample: {e}") from None
+    if inv_t == 0.0:
+        return masked_argmax(logits, mask, vocab, out, mask_idx)
+    _req(logits, torch.bfloat16, "truncated_sample.logits")
+    B, ld = logits.shape
+    V = vocab or ld
+    W = (V + 31) // 32
+    if V > ld:
+        raise HipOpsError("truncated_sample: vocab larger than row")
+    n_masks = 0
+    if mask is not None:
+        _req(mask, torch.int32, "truncated_sample.mask")
+        if mask_idx is not None:
+            _req(mask_idx, torch.int32, "truncated_sample.mask_idx")
+            if mask.dim() != 2 or mask.shape[1] != W or mask.shape[0] < 1 or mask_idx.numel() != B:
+                raise HipOpsError(f"truncated_sample: mask table {tuple(mask.shape)} / mask_idx {mask_idx.numel()} "
+                                  f"do not match B={B}, W={W}")
+            n_masks = mask.shape[0]
+        elif mask.shape != (B, W):
+            raise HipOpsError(f"truncated_sample: mask shape {tuple(mask.shape)} != {(B, W)}")
+    elif mask_idx is not None:
+        raise HipOpsError("truncated_sample: mask_idx given without a mask table")
+    if stats is not None:
+        _req_out(stats, torch.int32, 2 * B, "truncated_sample.stats")
+    out = torch.empty((B,), dtype=torch.int32, device=logits.device) if out is None else out
+    _req_out(out, torch.int32, B, "truncated_sample.out")
+    _check(lib().dmcp_truncated_sample(_ptr(logits), _ptr(mask), _ptr(mask_idx if mask is not None else None),
+                                       n_masks, _ptr(out), B, V, ld, _ptr(slots), _ptr(positions), seed, inv_t,
+                                       top_k, float(np.float32(top_p)), reference.ln_min_p(min_p), _ptr(stats),
+                                       _stream()), "dmcp_truncated_sample")
     return out
 
 

@@ -435,6 +435,159 @@ def lm_head_sample(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_i
     return masked_sample(logits, masks, w.shape[0], out, mask_idx, slots, positions, temperature, seed)
 
 
+# ---- top-k / top-p / min-p truncation of the sampled selection.  Per row: A =
+# the ids the mask allows (below vocab), x_v the bf16 logit widened to fp32,
+# x_max = max over A.  Every filter is a threshold on the VALUE (ties are kept
+# together, nothing depends on id order): kept = {v in A : x_v >= tau}, tau =
+# max(tau_k, tau_p, tau_m) with
+#   tau_k  the k-th largest x over A counting multiplicity; -inf when k = 0 or
+#          k >= |A|
+#   tau_p  over the top-k survivors (top-k, then top-p, as transformers
+#          orders them): walking the distinct values downwards and
+#          accumulating count(value) * exp((value - x_max) * fp32(1 / T)), the
+#          first value at which the running sum reaches p * Z, Z the
+#          survivors' total; -inf when p = 1
+#   tau_m  v is kept iff (x_v - x_max) * inv_t >= ln_min_p in fp32 (a
+#          subtract, then a multiply; ln_min_p = fp32(log(min_p)), the same
+#          bits on the host and in the kernel): tau_m is the lowest value of A
+#          that passes; -inf when min_p = 0
+# The chosen id is the argmax over the kept set of the scores of
+# :func:`sample_scores` (same hash, key and tie rule): with every filter off
+# it is :func:`masked_sample`'s.  csrc/truncate.hip follows these definitions.
+TOP_P_AMBIGUITY = 1e-4  # of Z: see truncation_threshold
+
+
+def truncation_args(top_k=0, top_p=1.0, min_p=0.0) -> tuple:
+    """The three truncation settings, validated: ``top_k`` an int >= 0 (0 =
+    off), 0 < ``top_p`` <= 1 (1 = off), 0 <= ``min_p`` < 1 (0 = off); a
+    ValueError names the offending knob.  Returns (top_k, top_p, min_p)."""
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0:
+        raise ValueError(f"top_k must be an integer >= 0, got {top_k!r}")
+    try:
+        p, m = float(top_p), float(min_p)
+    except (TypeError, ValueError):
+        raise ValueError(f"top_p / min_p must be numbers, got {top_p!r} / {min_p!r}") from None
+    if not (0.0 < p <= 1.0):
+        raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
+    if not (0.0 <= m < 1.0):
+        raise ValueError(f"min_p must be in [0, 1), got {min_p!r}")
+    return int(top_k), p, m
+
+
+def ln_min_p(min_p: float) -> float:
+    """fp32(log(min_p)) as the kernel and the reference compare against
+    (-inf for min_p = 0: nothing is cut)."""
+    return float(torch.tensor(math.log(min_p), dtype=torch.float32)) if min_p > 0 else float("-inf")
+
+
+def _allowed(logits: torch.Tensor, mask, vocab, mask_idx, slots) -> torch.Tensor:
+    B, ld = logits.shape
+    V = vocab or ld
+    ok = torch.ones((B, V), dtype=torch.bool, device=logits.device)
+    if mask is not None and mask_idx is not None:
+        mask = mask[mask_idx.long().clamp(0, mask.shape[0] - 1)]
+    if mask is not None:
+        idx = torch.arange(V, device=logits.device)
+        ok = ((mask.to(torch.int64)[:, idx // 32] >> (idx % 32)) & 1) != 0
+    return ok & (slots.long() >= 0)[:, None]
+
+
+def truncation_threshold(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, vocab: Optional[int] = None,
+                         mask_idx: Optional[torch.Tensor] = None, slots: Optional[torch.Tensor] = None,
+                         temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                         min_p: float = 0.0) -> tuple:
+    """(tau fp32 [B], kept count int64 [B], ambiguous bool [B]) of the
+    definitions above, thresholds in fp64 (the min-p comparison in fp32, as
+    defined).  tau is -inf where no filter is on, the mask allows nothing or
+    the row's slot is < 0.  A row is *ambiguous* when either running sum
+    adjacent to tau_p is within ``TOP_P_AMBIGUITY`` * Z of p * Z: an fp32 sum
+    of the same terms may then stop one value level earlier or later."""
+    B, ld = logits.shape
+    V = vocab or ld
+    top_k, top_p, min_p = truncation_args(top_k, top_p, min_p)
+    t = float(temperature)
+    if not math.isfinite(t) or t <= 0:
+        raise ValueError(f"truncation_threshold: temperature must be finite and > 0, got {temperature!r}")
+    if slots is None:
+        slots = torch.zeros(B, dtype=torch.int32, device=logits.device)
+    inv_t = float(torch.tensor(1.0 / t, dtype=torch.float32))
+    x = logits[:, :V].to(torch.bfloat16).float() + 0.0  # -0 -> +0: a threshold on the value
+    ok = _allowed(logits, mask, V, mask_idx, slots)
+    tau = torch.full((B,), float("-inf"), dtype=torch.float32)
+    kept = torch.zeros(B, dtype=torch.int64)
+    amb = torch.zeros(B, dtype=torch.bool)
+    lnm = ln_min_p(min_p)
+    for b in range(B):
+        xa = x[b][ok[b]]
+        n = xa.numel()
+        if n == 0:
+            continue
+        x_max = xa.max()
+        tk = tp = tm = float("-inf")
+        if 0 < top_k < n:
+            tk = float(torch.topk(xa, top_k).values[-1])
+        if top_p < 1.0:
+            vals, counts = torch.unique(xa[xa >= tk], return_counts=True)  # ascending
+            vals, counts = vals.flip(0), counts.flip(0)
+            cum = torch.cumsum(counts.double() * torch.exp((vals.double() - float(x_max)) * inv_t), 0)
+            z = float(cum[-1])
+            i = min(int(torch.searchsorted(cum, torch.tensor(top_p * z, dtype=torch.float64))), vals.numel() - 1)
+            tp = float(vals[i])
+            near = [float(cum[i])] + ([float(cum[i - 1])] if i > 0 else [])
+            amb[b] = any(abs(s - top_p * z) <= TOP_P_AMBIGUITY * z for s in near)
+        if min_p > 0.0:
+            tm = float(xa[(xa - x_max) * inv_t >= lnm].min())
+        tau[b] = max(tk, tp, tm)
+        kept[b] = int((xa >= tau[b]).sum())
+    return tau, kept, amb
+
+
+def tau_bits(tau: torch.Tensor) -> torch.Tensor:
+    """The bf16 bit patterns (int32, 0 .. 0xFFFF) of thresholds, as the kernel reports them."""
+    return tau.to(torch.bfloat16).view(torch.int16).to(torch.int32) & 0xFFFF
+
+
+def truncated_sample_at(tau: torch.Tensor, logits: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                        vocab: Optional[int] = None, mask_idx: Optional[torch.Tensor] = None,
+                        slots: Optional[torch.Tensor] = None, positions: Optional[torch.Tensor] = None,
+                        temperature: float = 1.0, seed: int = 0) -> tuple:
+    """(ids int32 [B], kept count [B]) of the sampled selection over the
+    allowed ids whose value is >= ``tau`` (fp32 [B]): what
+    :func:`truncated_sample` returns for its own thresholds, and the expected
+    result at a neighbouring value level for a row whose top-p sum is
+    ambiguous."""
+    V = vocab or logits.shape[1]
+    scores = sample_scores(logits, mask, vocab, mask_idx, slots, positions, temperature, seed)
+    cut = logits[:, :V].to(torch.bfloat16).float() < tau.to(torch.float32).to(logits.device)[:, None]
+    kept = (_allowed(logits, mask, V, mask_idx, slots) & ~cut).sum(dim=1)
+    scores[cut] = float("-inf")
+    return torch.argmax(scores, dim=-1).to(torch.int32), kept  # first index among ties; 0 for an all -inf row
+
+
+def truncated_sample(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, vocab: Optional[int] = None,
+                     out: Optional[torch.Tensor] = None, mask_idx: Optional[torch.Tensor] = None,
+                     slots: Optional[torch.Tensor] = None, positions: Optional[torch.Tensor] = None,
+                     temperature: float = 0.0, seed: int = 0, top_k: int = 0, top_p: float = 1.0,
+                     min_p: float = 0.0, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`masked_sample` over the ids :func:`truncation_threshold` keeps:
+    the kept id with the highest score of :func:`sample_scores`, the lowest id
+    among ties, 0 when nothing is allowed or the row's slot is < 0.
+    Temperature 0 is :func:`masked_argmax` (the greedy id survives every
+    truncation; ``stats`` is not written).  ``stats`` int32 [B, 2] receives
+    the bf16 bits of tau and the kept count."""
+    top_k, top_p, min_p = truncation_args(top_k, top_p, min_p)
+    if _sample_args(logits.shape[0], slots, positions, temperature) == 0:
+        return masked_argmax(logits, mask, vocab, out, mask_idx)
+    tau, kept, _ = truncation_threshold(logits, mask, vocab, mask_idx, slots, temperature, top_k, top_p, min_p)
+    ids, _ = truncated_sample_at(tau, logits, mask, vocab, mask_idx, slots, positions, temperature, seed)
+    if stats is not None:
+        stats.copy_(torch.stack([tau_bits(tau), kept.to(torch.int32)], dim=1).to(stats.device))
+    if out is not None:
+        out.copy_(ids)
+        return out
+    return ids
+
+
 def embedding(table: torch.Tensor, ids: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     y = table[ids.long().clamp(0, table.shape[0] - 1)]
     if out is not None:

@@ -6,7 +6,10 @@ calls (no Python wrapper cost).  One JSON line per op and shape.
   python scripts/bench_sampling.py [--rows 512 610] [--vocab 128256] [--hidden 2048]
 
 Rows <= 512 time lm_head_sample (wgemm.hip), rows above it tgemm_lm_head_sample
-(tgemm.hip); --masked-rows time masked_sample over [rows, vocab] bf16 logits.
+(tgemm.hip); --masked-rows time masked_sample over [rows, vocab] bf16 logits;
+--truncated-rows time truncated_sample (csrc/truncate.hip) over the same kind
+of logits with --top-k / --top-p / --min-p against masked_sample at the same
+temperature (the untruncated draw), alternated the same way.
 """
 import argparse
 import json
@@ -43,11 +46,16 @@ def _timed(fn, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rows", type=int, nargs="+", default=[512, 610])
+    ap.add_argument("--rows", type=int, nargs="*", default=[512, 610])
     ap.add_argument("--masked-rows", type=int, nargs="*", default=[16, 64])
     ap.add_argument("--vocab", type=int, default=128256)
     ap.add_argument("--hidden", type=int, default=2048)
     ap.add_argument("--temperature", type=float, default=0.7)
+    ap.add_argument("--truncated-rows", type=int, nargs="*", default=[])
+    ap.add_argument("--top-k", type=int, default=20)
+    ap.add_argument("--top-p", type=float, default=0.95)
+    ap.add_argument("--min-p", type=float, default=0.0)
+    ap.add_argument("--logit-scale", type=float, default=2.5, help="std of the random logits of --truncated-rows")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args()
@@ -90,6 +98,28 @@ def main():
         out = torch.empty(B, dtype=torch.int32, device="cuda")
         report("masked_sample", B, lambda mi, s, p, t: lambda: hip.masked_sample(
             logits, masks, V, out, mi, s, p, t, 1))
+    for B in args.truncated_rows:
+        logits = (torch.randn(B, V, device="cuda", generator=g) * args.logit_scale).to(torch.bfloat16)
+        out = torch.empty(B, dtype=torch.int32, device="cuda")
+        midx = torch.randint(0, 8, (B,), device="cuda", dtype=torch.int32, generator=g)
+        slots = torch.randint(0, 768, (B,), device="cuda", dtype=torch.int32, generator=g)
+        pos = torch.randint(0, 8192, (B,), device="cuda", dtype=torch.int32, generator=g)
+        runs = {"masked_sample": _timed(lambda: hip.masked_sample(logits, masks, V, out, midx, slots, pos, T, 1),
+                                        args.reps),
+                "truncated_sample": _timed(lambda: hip.truncated_sample(
+                    logits, masks, V, out, midx, slots, pos, T, 1, args.top_k, args.top_p, args.min_p), args.reps)}
+        us = {k: [] for k in runs}
+        for _ in range(args.rounds):
+            for k, run in runs.items():
+                us[k].append(round(run(), 2))
+        med = {k: sorted(v)[len(v) // 2] for k, v in us.items()}
+        print(json.dumps({"bench": "truncated_sample", "rows": B, "vocab": V, "temperature": T, "top_k": args.top_k,
+                          "top_p": args.top_p, "min_p": args.min_p, "logit_scale": args.logit_scale,
+                          "masked_sample_us": us["masked_sample"], "truncated_sample_us": us["truncated_sample"],
+                          "masked_sample_median_us": med["masked_sample"],
+                          "truncated_sample_median_us": med["truncated_sample"],
+                          "row_bytes_read_per_call": 2 * V * (2 + 4 * bool(0 < args.top_k) + 4 * (args.top_p < 1))}),
+              flush=True)
 
 
 if __name__ == "__main__":
