@@ -91,6 +91,11 @@ class Config:
     local_llm_top_k: int = 0
     local_llm_top_p: float = 1.0
     local_llm_min_p: float = 0.0
+    # repetition penalty (finite, > 0; 1.0 = off) and presence penalty (finite;
+    # 0.0 = off) over the tokens of the reply so far, at any temperature --
+    # dmcp/ops/reference.py penalize.  Checked when the engine is built.
+    local_llm_repetition_penalty: float = 1.0
+    local_llm_presence_penalty: float = 0.0
     local_llm_devices: str = "all"
     # "process": one worker process per GPU, started before this process
     # touches HIP (the service default); "inline": engines in this process
@@ -173,6 +178,8 @@ class Config:
             "LOCAL_LLM_TOP_K": "local_llm_top_k",
             "LOCAL_LLM_TOP_P": "local_llm_top_p",
             "LOCAL_LLM_MIN_P": "local_llm_min_p",
+            "LOCAL_LLM_REPETITION_PENALTY": "local_llm_repetition_penalty",
+            "LOCAL_LLM_PRESENCE_PENALTY": "local_llm_presence_penalty",
             "LOCAL_LLM_DEVICES": "local_llm_devices",
             "LOCAL_LLM_WORKERS": "local_llm_workers",
             "LOCAL_LLM_MAX_BATCH": "local_llm_max_batch",

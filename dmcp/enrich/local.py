@@ -53,7 +53,7 @@ from typing import Any, Deque, Dict, Iterable, Iterator, List, Optional, Sequenc
 import torch
 
 from ..models.llm import LocalLM, LMConfig, DecodeGraphs, preset
-from ..ops.reference import truncation_args
+from ..ops.reference import penalty_settings, truncation_args
 from .backend import SYNTHETIC_PREFIX, EnrichmentBackend, build_enrichment_prompt
 from .jsonfix import parse_enrichment_response
 from .tokenizer import ByteTokenizer
@@ -515,8 +515,10 @@ class LocalEngine:
                  fork_methods: bool = True, fork_max_context: int = 0,
                  reply_shape: Optional[ReplyShape] = None, type_choice: Optional[bool] = None,
                  precapture: Optional[bool] = None, temperature: float = 0.0, seed: int = 0,
-                 top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0) -> None:
+                 top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0,
+                 repetition_penalty: float = 1.0, presence_penalty: float = 0.0) -> None:
         self.model = model
+        self.repetition_penalty, self.presence_penalty = penalty_settings(repetition_penalty, presence_penalty)
         # temperature 0 (the default) is the greedy selection, unchanged; above
         # it every selected token -- the decode steps' and the first one after
         # a prefill -- is a draw from softmax(logits / temperature) over the
@@ -590,6 +592,30 @@ class LocalEngine:
         self._choice_rows: Dict[Tuple[int, bytes], int] = {}
         masks = list(self.tok.json_masks(self.cfg.vocab_size)) + self._choice_masks()
         self.masks = torch.tensor(masks, dtype=torch.int32, device=dev)
+        # repetition / presence penalty over the reply so far (1.0 / 0.0:
+        # off -- no history table, no extra launch, every path as before; it
+        # works at temperature 0, where the loops are).  The history of a
+        # sequence lives on the device, one bitset row per KV slot
+        # (dmcp.ops.history_mark, first in every decode step).  Only the two
+        # free-text masks are penalised: class-type correction and the step
+        # count are decisions, not prose.  The lone quote is never recorded:
+        # once one string had been closed, closing the next would be
+        # penalised and strings would run to their caps.  The first
+        # selection after a prefill has an empty history and stays on the
+        # unpenalised ops.
+        self._penalty = None
+        if (self.repetition_penalty, self.presence_penalty) != (1.0, 0.0):
+            flags = [0] * len(masks)
+            flags[self.MASK_NO_QUOTE] = flags[self.MASK_QUOTE] = 1
+            exempt = [0] * ((self.cfg.vocab_size + 31) // 32)
+            if 0 <= self._quote < self.cfg.vocab_size:
+                w = exempt[self._quote >> 5] | (1 << (self._quote & 31))
+                exempt[self._quote >> 5] = w - (1 << 32) if w >= (1 << 31) else w
+            self._penalty = (self.repetition_penalty, self.presence_penalty,
+                             torch.tensor(flags, dtype=torch.int32, device=dev),
+                             torch.tensor(exempt, dtype=torch.int32, device=dev))
+            self._sample_kw["penalty"] = self._penalty
+            model.reserve_history()
         self.graphs = DecodeGraphs(model, self.masks, alt_token=self._quote, **self._sample_kw) \
             if use_graphs and dev.type == "cuda" else None
         # every row-count bucket's decode graph captured now, at engine start:
@@ -1135,12 +1161,24 @@ class LocalEngine:
             return merge_branches(got[0], got[1:])  # type: ignore[arg-type]
         return merge_parts(got)  # type: ignore[arg-type]
 
+    def _history_reset(self, slots: List[int]) -> None:
+        """A newly assigned slot starts from an empty penalty history: queued
+        on the engine's stream, ahead of the first step that carries the slot
+        (no host synchronisation).  Pipelined rows launched earlier for a
+        sequence that turns out to have finished may still mark its slot
+        after it was released -- harmless: they are ahead of this reset on
+        the stream, and nothing reads a free slot's row."""
+        if self._penalty is not None and slots:
+            from .. import ops
+            ops.history_reset(self.model.history, slots)
+
     def _start_branches(self, st: "_Fork", slots: List[int], src: Optional[int]) -> List[_Seq]:
         """Starts the next pending branches of ``st`` in ``slots`` -- with a copy
         of the head's own KV from sibling slot ``src`` (None: the slots
         already hold it: the head's, or a finished sibling's) -- admitted."""
         head, pos = st.head, st.pos
         kids = []
+        self._history_reset(slots)  # a branch does not inherit its head's history (branch 0 in its slot included)
         for slot in slots:
             j, segs = st.pending.popleft()
             q = _Seq(head.inp, head.index, segs, part=1 + j, n_parts=head.n_parts)
@@ -1331,6 +1369,7 @@ class LocalEngine:
                 batch.append(s)
                 users += s.shared
                 ntok += nxt
+            self._history_reset([q.slot for q in batch])
             admits.append(self._admit_launch(batch))
             clock.lap("admit_launch")
 

@@ -674,7 +674,9 @@ def engine_spec(cfg) -> dict:
             "seed": int(getattr(cfg, "local_llm_seed", 0)),
             "top_k": int(getattr(cfg, "local_llm_top_k", 0)),
             "top_p": float(getattr(cfg, "local_llm_top_p", 1.0)),
-            "min_p": float(getattr(cfg, "local_llm_min_p", 0.0))}
+            "min_p": float(getattr(cfg, "local_llm_min_p", 0.0)),
+            "repetition_penalty": float(getattr(cfg, "local_llm_repetition_penalty", 1.0)),
+            "presence_penalty": float(getattr(cfg, "local_llm_presence_penalty", 0.0))}
 
 
 # ------------------------------------------------------------------ child

@@ -525,6 +525,7 @@ class LocalLM:
         # reserve_truncation_logits(), only when a filter is configured
         # (263 MB at 1,024 x 128,256)
         self.trunc_logits: Optional[torch.Tensor] = None
+        self.history: Optional[torch.Tensor] = None  # reserve_history()
         # fp8 prefill: e4m3 copies of the four projections (per-row scales),
         # quantised once; the batched prefill then runs on csrc/pgemm.hip
         # (the CPU references take any dims the 32-element blocks divide)
@@ -1155,6 +1156,34 @@ class LocalLM:
                                             device=self.device)
         return self.trunc_logits
 
+    def reserve_history(self) -> torch.Tensor:
+        """The token history of the repetition / presence penalty (int32
+        [num_slots, ceil(vocab / 32)] bitset rows, :func:`dmcp.ops.history_mark`;
+        12.3 MB at 768 slots x 128,256 ids), allocated zeroed on the first
+        call: an engine with a penalty configured calls it when it is built,
+        before any graph is captured."""
+        if self.history is None:
+            self.history = torch.zeros((self.num_slots, (self.cfg.vocab_size + 31) // 32), dtype=torch.int32,
+                                       device=self.device)
+        return self.history
+
+    def _step_penalty(self, penalty: Optional[tuple], tokens: torch.Tensor, slots: torch.Tensor,
+                      src: Optional[torch.Tensor] = None, last_ids: Optional[torch.Tensor] = None):
+        """The first op of a penalised decode step: record the tokens the step
+        feeds (before the head overwrites ``last_ids``, and so that this
+        step's selection sees the token just fed) and return the
+        :class:`dmcp.ops.Penalty` of its selection.  ``penalty`` = (theta,
+        alpha, flags per mask row or None, exempt bitset or None); None, or
+        theta 1 and alpha 0: nothing is launched and None is returned."""
+        if penalty is None or (penalty[0] == 1 and penalty[1] == 0):
+            return None
+        theta, alpha, flags, exempt = penalty
+        hist = self.reserve_history()
+        ops.history_mark(hist, tokens, slots, src, last_ids if src is not None else None, exempt,
+                         self.cfg.vocab_size)
+        # the slots are the step's own, inside the KV cache: no read-back to check them
+        return ops.Penalty(hist, slots, theta, alpha, flags, check_slots=False)
+
     def _head_into(self, h: torch.Tensor, buf: torch.Tensor) -> torch.Tensor:
         """The LM head's logits of a decode step written to ``buf[:rows]``:
         the large-tile GEMM from TGEMM_HEAD_MIN_ROWS rows where the fused
@@ -1170,7 +1199,7 @@ class LocalLM:
 
     def decode_select(self, tokens: torch.Tensor, slots: torch.Tensor, positions: torch.Tensor,
                       masks: torch.Tensor, mask_idx: torch.Tensor, sample: Optional[tuple] = None,
-                      truncate: Optional[tuple] = None) -> tuple:
+                      truncate: Optional[tuple] = None, penalty: Optional[tuple] = None) -> tuple:
         """:meth:`decode` + selection under a per-row grammar mask
         (``masks`` [M, ceil(V/32)] bitsets, ``mask_idx`` int32 [B]): greedy,
         or with ``sample`` = (temperature, seed) a draw from softmax(logits /
@@ -1178,25 +1207,30 @@ class LocalLM:
         position (:func:`dmcp.ops.masked_sample`; temperature 0 is greedy);
         ``truncate`` = (top_k, top_p, min_p) restricts that draw
         (:func:`dmcp.ops.truncated_sample`; ignored when greedy).
-        Returns (logits, ids int32 [B]); capturable."""
+        ``penalty`` = (theta, alpha, flags per mask row, exempt bitset): the
+        repetition / presence penalty over the tokens fed to each slot
+        (:meth:`_step_penalty`: one more launch, first in the step; works at
+        temperature 0 too).  Returns (logits, ids int32 [B]); capturable."""
+        pen = {} if (p := self._step_penalty(penalty, tokens, slots)) is None else {"penalty": p}
         logits = self.decode(tokens, slots, positions)
         cut = _truncation(sample, truncate)
         if cut is not None:
             ids = ops.truncated_sample(logits, masks, vocab=self.cfg.vocab_size, mask_idx=mask_idx, slots=slots,
                                        positions=positions, temperature=sample[0], seed=sample[1], top_k=cut[0],
-                                       top_p=cut[1], min_p=cut[2])
+                                       top_p=cut[1], min_p=cut[2], **pen)
         elif sample is not None:
             ids = ops.masked_sample(logits, masks, vocab=self.cfg.vocab_size, mask_idx=mask_idx, slots=slots,
-                                    positions=positions, temperature=sample[0], seed=sample[1])
+                                    positions=positions, temperature=sample[0], seed=sample[1], **pen)
         else:
-            ids = ops.masked_argmax(logits, masks, vocab=self.cfg.vocab_size, mask_idx=mask_idx)
+            ids = ops.masked_argmax(logits, masks, vocab=self.cfg.vocab_size, mask_idx=mask_idx, **pen)
         return logits, ids
 
     def decode_select_gather(self, tokens: torch.Tensor, src: torch.Tensor, last_ids: torch.Tensor,
                              slots: torch.Tensor, positions: torch.Tensor, masks: torch.Tensor,
                              mask_idx: torch.Tensor, mask_alt: Optional[torch.Tensor] = None,
                              alt_token: int = -1, prefix_rows: Optional[torch.Tensor] = None,
-                             sample: Optional[tuple] = None, truncate: Optional[tuple] = None) -> tuple:
+                             sample: Optional[tuple] = None, truncate: Optional[tuple] = None,
+                             penalty: Optional[tuple] = None) -> tuple:
         """:meth:`decode_select` whose input token of row r is ``last_ids[src[r]]``
         where ``src[r] >= 0`` (the previous step's selection, still on the
         device) and ``tokens[r]`` otherwise; the step's own selections are
@@ -1210,10 +1244,15 @@ class LocalLM:
         its bf16 logits with the plain GEMM (:meth:`_head_into`, into the
         buffer of :meth:`reserve_truncation_logits`) and selects with
         :func:`dmcp.ops.truncated_sample`, as many kernels as the fused head
-        and its pair reduction; the logits are returned.  Capturable."""
+        and its pair reduction; the logits are returned.  ``penalty``: as
+        :meth:`decode_select` -- the gathered tokens are recorded first, then
+        whichever selection the step takes (a fused head, the <= 16-row path
+        or the truncation path) runs its penalised variant.  Capturable."""
         B = tokens.shape[0]
         keys = {} if sample is None else {"slots": slots, "positions": positions, "temperature": sample[0],
                                           "seed": sample[1]}
+        if (p := self._step_penalty(penalty, tokens, slots, src, last_ids)) is not None:
+            keys["penalty"] = p
         cut = _truncation(sample, truncate)
         if cut is not None:
             keys.update(top_k=cut[0], top_p=cut[1], min_p=cut[2])
@@ -1353,7 +1392,8 @@ class DecodeGraphs:
     def __init__(self, model: LocalLM, masks: torch.Tensor,
                  buckets: Sequence[int] = (1, 2, 4, 8, 16, 32, 64, 96, 128, 192, 256, 320, 384, 448, 512, 640,
                                           768, 896, 1024), alt_token: int = -1,
-                 sample: Optional[tuple] = None, truncate: Optional[tuple] = None) -> None:
+                 sample: Optional[tuple] = None, truncate: Optional[tuple] = None,
+                 penalty: Optional[tuple] = None) -> None:
         self.model = model
         self.masks = masks
         self.alt_token = int(alt_token)
@@ -1365,6 +1405,13 @@ class DecodeGraphs:
         self.truncate = truncate
         if _truncation(sample, truncate) is not None:
             model.reserve_truncation_logits()  # before any capture
+        # (theta, alpha, flags per mask row, exempt bitset) of that engine's
+        # repetition / presence penalty, a constant of the capture like the
+        # two above: the graph gains one kernel node (history_mark); None, or
+        # theta 1 and alpha 0: the graph is the unpenalised one, node for node
+        self.penalty = None if penalty is None or (penalty[0] == 1 and penalty[1] == 0) else penalty
+        if self.penalty is not None:
+            model.reserve_history()  # before any capture
         self.timing = {"sync_s": 0.0, "replay_s": 0.0}  # host time inside run(): staging wait, H2D + launch
         # device witness: graph replays and the kernel nodes they launched
         self.counts = {"graph_replays": 0, "graph_kernels": 0}
@@ -1406,14 +1453,15 @@ class DecodeGraphs:
         with torch.cuda.stream(s):
             for _ in range(2):  # warm up hipBLASLt heuristics / allocator outside capture
                 m.decode_select_gather(inp[0], inp[4], scratch, inp[1], inp[2], self.masks, inp[3], inp[5],
-                                       self.alt_token, inp[6], self.sample, self.truncate)
+                                       self.alt_token, inp[6], self.sample, self.truncate, self.penalty)
         torch.cuda.current_stream().wait_stream(s)
         # keep_graph: the hipGraph_t stays queryable after capture (the kernel
         # node count of the witness); instantiated explicitly right after
         g = torch.cuda.CUDAGraph(keep_graph=True)
         with torch.cuda.graph(g):
             logits, ids = m.decode_select_gather(inp[0], inp[4], self.last_ids, inp[1], inp[2], self.masks, inp[3],
-                                                 inp[5], self.alt_token, inp[6], self.sample, self.truncate)
+                                                 inp[5], self.alt_token, inp[6], self.sample, self.truncate,
+                                                 self.penalty)
         bucket = _Bucket(g, inp, logits, ids, b)
         g.instantiate()
         self.graphs[b] = bucket
@@ -1440,7 +1488,8 @@ class DecodeGraphs:
                               list(prefix_rows)], dtype=torch.int32, device=m.device)
             return m.decode_select_gather(t[0].contiguous(), t[4].contiguous(), self.last_ids, t[1].contiguous(),
                                           t[2].contiguous(), self.masks, t[3].contiguous(), t[5].contiguous(),
-                                          self.alt_token, t[6].contiguous(), self.sample, self.truncate)
+                                          self.alt_token, t[6].contiguous(), self.sample, self.truncate,
+                                          self.penalty)
         b = self.bucket_for(n)
         if b not in self.graphs:
             self._capture(b)

@@ -20,6 +20,7 @@ from .hip import (PGEMM_TILE_N, WMX_MAX_ROWS, pgemm_supported, wgemm_mx_resid_no
                   wgemm_mx_swiglu, wmx_plan)
 from .hip import (TGEMM_MAX_ROWS, tgemm, tgemm_lm_head_argmax, tgemm_lm_head_sample,  # noqa: F401
                   tgemm_resid_norm, tgemm_rope_kv, tgemm_swiglu, wgemm)
+from .reference import Penalty, penalize  # noqa: F401
 from .reference import SharedPrefix, mx_dequant, quantize_weight, rope_tables, weight_dequant  # noqa: F401
 
 
@@ -46,11 +47,14 @@ def _by_device(name: str):
 
 # ops with an fp32 CPU reference: norms, RoPE + KV append, prefill attention,
 # SwiGLU, selection (greedy, sampled at a temperature, and sampled under
-# top-k / top-p / min-p truncation), embedding, the
+# top-k / top-p / min-p truncation; each optionally under a repetition /
+# presence penalty, whose history table history_mark / history_reset keep),
+# embedding, the
 # decode step's input gather + first norm, the MXFP8 prefill path
 # (csrc/pgemm.hip), and the three fused QKV projections (their references
 # define where the optional bias and QK-norm enter)
-DEVICE_OPS = ("add_rmsnorm", "rope_kv", "prefill_attention", "prefill_attention_varlen", "silu_mul",
+DEVICE_OPS = ("history_mark", "history_reset",
+              "add_rmsnorm", "rope_kv", "prefill_attention", "prefill_attention_varlen", "silu_mul",
               "masked_argmax", "lm_head_argmax", "masked_sample", "lm_head_sample", "truncated_sample", "embedding",
               "decode_embed_norm",
               "mx_quant", "rmsnorm_mx", "pgemm", "pgemm_resid", "pgemm_swiglu", "pgemm_qkv", "fused_rope_kv",

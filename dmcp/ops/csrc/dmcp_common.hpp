@@ -257,6 +257,46 @@ inline sample_keys_t<SAMPLE> pick_keys(const SampleKeys& sk) {
     else return {};
 }
 
+// ---- repetition / presence penalty (dmcp/ops/reference.py penalize): an
+// allowed id whose bit is set in the row's history (a bitset row per KV slot,
+// hwords words each) competes with
+//   x' = bf16_rne((x > 0 ? x * inv_theta : x * theta) - alpha)
+// instead of its bf16 logit x; everything downstream (argmax, Gumbel score,
+// truncation keys) works on x' unchanged.  The multiply and the subtract are
+// rounded separately (no fma contraction), as the reference's two fp32 ops.
+__device__ __forceinline__ float penalize(float x, float theta, float inv_theta, float alpha) {
+    const float y = __fsub_rn(x > 0.f ? __fmul_rn(x, inv_theta) : __fmul_rn(x, theta), alpha);
+    return bf2f(f2bf(y));
+}
+
+// The PENAL variants' extra kernel argument; the other instantiations take an
+// empty struct, so their code does not change.  A row is penalised when its
+// slot is in [0, n_slots) and its mask row's flag (rows, optional) is set.
+struct PenaltyKeys {
+    const uint32_t* history;  // [n_slots, hwords]
+    const int32_t* slots;     // [rows of the launch]
+    const int32_t* rows;      // per mask row flags, nullptr = every row
+    int hwords, n_slots, n_rows;
+    float theta, inv_theta, alpha;
+};
+struct NoPenaltyKeys {};
+template <bool PENAL>
+using penalty_keys_t = std::conditional_t<PENAL, PenaltyKeys, NoPenaltyKeys>;
+template <bool PENAL>
+inline penalty_keys_t<PENAL> pick_penalty(const PenaltyKeys& pk) {
+    if constexpr (PENAL) return pk;
+    else return {};
+}
+
+// the history row of launch row m under mask row mr, nullptr when the row is
+// not penalised (padding, a slot outside the table, a choice mask)
+__device__ __forceinline__ const uint32_t* penalty_row(const PenaltyKeys& pk, int m, int mr) {
+    const int slot = pk.slots[m];
+    if (slot < 0 || slot >= pk.n_slots) return nullptr;
+    if (pk.rows && (mr < 0 || mr >= pk.n_rows || pk.rows[mr] == 0)) return nullptr;
+    return pk.history + (size_t)slot * pk.hwords;
+}
+
 // the selection kernels' merge rule: the highest value, the lowest id among ties
 __device__ __forceinline__ void argmax_take(float x, int v, float& best, int& bi) {
     if (x > best || (x == best && v < bi)) { best = x; bi = v; }

@@ -336,12 +336,19 @@ constexpr int MA_T = 1024, MA_U = 2;
 // keyed by (seed, the row's slot, its position, the id) -- the hash and the
 // two logs only for the ids the mask allows; a row with slot < 0 selects 0.
 // The greedy instantiation takes an empty struct and compiles as before.
-template <bool SAMPLE>
+//
+// PENAL: the repetition / presence penalty (dmcp_common.hpp penalize): the
+// row's history byte of an 8-id chunk is loaded with its mask byte (same word
+// index, same shift), and an allowed id whose history bit is set competes
+// with its penalised value -- before the noise, when SAMPLE.  The row's slot
+// comes from the penalty's own slots (the greedy form has no sampling keys).
+template <bool SAMPLE, bool PENAL = false>
 __global__ __launch_bounds__(MA_T) void masked_argmax_kernel(const uint16_t* __restrict__ logits,
                                                             const uint32_t* __restrict__ mask,
                                                             const int32_t* __restrict__ mask_idx, int n_masks,
                                                             int32_t* __restrict__ ids, int V, int ld, int nch,
-                                                            sample_keys_t<SAMPLE> sk) {
+                                                            sample_keys_t<SAMPLE> sk,
+                                                            penalty_keys_t<PENAL> pk) {
     const int b = blockIdx.x;
     uint32_t key = 0;
     float inv_t = 1.f;
@@ -361,6 +368,8 @@ __global__ __launch_bounds__(MA_T) void masked_argmax_kernel(const uint16_t* __r
         mr = mr < 0 ? 0 : (mr >= n_masks ? n_masks - 1 : mr);
     }
     const uint32_t* mrow = mask ? mask + (size_t)mr * ((V + 31) >> 5) : nullptr;
+    const uint32_t* hrow = nullptr;  // block-uniform
+    if constexpr (PENAL) hrow = penalty_row(pk, b, mr);
     float bv[8];
     int bc[8];  // chunk index of bv[j] (id = 8 * chunk + j)
 #pragma unroll
@@ -368,11 +377,13 @@ __global__ __launch_bounds__(MA_T) void masked_argmax_kernel(const uint16_t* __r
     for (int c0 = threadIdx.x; c0 < nch; c0 += MA_T * MA_U) {
         uint4 q[MA_U];
         uint32_t mb[MA_U];
+        [[maybe_unused]] uint32_t hb[MA_U];
 #pragma unroll
         for (int u = 0; u < MA_U; ++u) {
             const int c = min(c0 + u * MA_T, nch - 1);
             q[u] = *reinterpret_cast<const uint4*>(row + (size_t)c * 8);
             mb[u] = mrow ? (mrow[c >> 2] >> ((c & 3) * 8)) & 0xFFu : 0xFFu;
+            if constexpr (PENAL) hb[u] = hrow ? (hrow[c >> 2] >> ((c & 3) * 8)) & 0xFFu : 0u;
         }
 #pragma unroll
         for (int u = 0; u < MA_U; ++u) {
@@ -382,6 +393,9 @@ __global__ __launch_bounds__(MA_T) void masked_argmax_kernel(const uint16_t* __r
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 float x = __uint_as_float((j & 1) ? (w[j >> 1] & 0xFFFF0000u) : (w[j >> 1] << 16));
+                if constexpr (PENAL) {
+                    if (((m & hb[u]) >> j) & 1u) x = penalize(x, pk.theta, pk.inv_theta, pk.alpha);
+                }
                 if constexpr (SAMPLE) {
                     if ((m >> j) & 1u) x = gumbel_score(x, inv_t, key, c * 8 + j);
                     else x = -INFINITY;
@@ -402,6 +416,9 @@ __global__ __launch_bounds__(MA_T) void masked_argmax_kernel(const uint16_t* __r
     for (int v = nch * 8 + threadIdx.x; v < V; v += MA_T) {
         if (mrow && !((mrow[v >> 5] >> (v & 31)) & 1u)) continue;
         float x = bf2f(row[v]);
+        if constexpr (PENAL) {
+            if (hrow && ((hrow[v >> 5] >> (v & 31)) & 1u)) x = penalize(x, pk.theta, pk.inv_theta, pk.alpha);
+        }
         if constexpr (SAMPLE) x = gumbel_score(x, inv_t, key, v);
         argmax_take(x, v, best, bi);
     }
@@ -421,6 +438,53 @@ __global__ __launch_bounds__(MA_T) void masked_argmax_kernel(const uint16_t* __r
         for (int k = 1; k < MA_T / kWave; ++k) argmax_take(sb[k], si[k], B, I);
         ids[b] = (I == 0x7fffffff) ? 0 : I;
     }
+}
+
+// --------------------------------------------------------------------------
+// 5b. the penalty's history (dmcp_common.hpp PenaltyKeys): one bitset row of
+//    hwords words per KV slot; bit v is set once token v has been fed to the
+//    slot by a decode row.  history_mark_kernel runs first in a decode step,
+//    one thread per row: the row's token by decode_embed_norm_kernel's gather
+//    (src[r] >= 0 ? last_ids[src[r]] : tokens[r] -- before the head
+//    overwrites last_ids), skipped when the row is padding (slot < 0, or
+//    outside the table), the token is outside [0, V) or its bit is set in
+//    `exempt`.  Several rows of a step can share a slot (jump-forward) and a
+//    word: an integer atomicOr, whose result does not depend on the order.
+// --------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void history_mark_kernel(uint32_t* __restrict__ history, int hwords, int n_slots,
+                                                             const int32_t* __restrict__ tokens,
+                                                             const int32_t* __restrict__ slots,
+                                                             const int32_t* __restrict__ src,
+                                                             const int32_t* __restrict__ last_ids, int n_last,
+                                                             const uint32_t* __restrict__ exempt, int rows, int V) {
+    const int r = blockIdx.x * kBlock + threadIdx.x;
+    if (r >= rows) return;
+    const int slot = slots[r];
+    if (slot < 0 || slot >= n_slots) return;
+    int id = tokens[r];
+    if (src) {
+        const int s = src[r];
+        if (s >= 0) id = last_ids[s < n_last ? s : n_last - 1];
+    }
+    if (id < 0 || id >= V) return;  // V <= 32 * hwords (checked at the entry point)
+    const uint32_t bit = 1u << (id & 31);
+    if (exempt && (exempt[id >> 5] & bit)) return;
+    atomicOr(history + (size_t)slot * hwords + (id >> 5), bit);
+}
+
+// zero the history rows of up to HR_MAX slots (passed by value: no device
+// index tensor, no copy, no synchronisation -- the engine resets a slot where
+// it assigns it, ahead of the first step that carries it)
+constexpr int HR_MAX = 64;
+struct HistorySlots {
+    int32_t s[HR_MAX];
+};
+__global__ __launch_bounds__(kBlock) void history_reset_kernel(uint32_t* __restrict__ history, int hwords, int n_slots,
+                                                              HistorySlots hs) {
+    const int slot = hs.s[blockIdx.y];
+    const int w = blockIdx.x * kBlock + threadIdx.x;
+    if (slot < 0 || slot >= n_slots || w >= hwords) return;
+    history[(size_t)slot * hwords + w] = 0u;
 }
 
 // --------------------------------------------------------------------------
@@ -1124,8 +1188,73 @@ int dmcp_masked_argmax(const void* logits, const void* mask, const void* mask_id
     const bool vec = (ld % 8 == 0) && (reinterpret_cast<uintptr_t>(logits) % 16 == 0);
     masked_argmax_kernel<false><<<B, MA_T, 0, (hipStream_t)stream>>>(
         (const uint16_t*)logits, (const uint32_t*)mask, (const int32_t*)mask_idx, n_masks, (int32_t*)ids, V, ld,
-        vec ? V / 8 : 0, NoSampleKeys{});
+        vec ? V / 8 : 0, NoSampleKeys{}, NoPenaltyKeys{});
     return hipGetLastError();
+}
+
+// dmcp_masked_argmax (inv_temperature == 0; slots / positions / seed unused)
+// or dmcp_masked_sample (inv_temperature > 0) under a repetition / presence
+// penalty (dmcp_common.hpp penalize): history uint32 [n_slots, hwords] bitset
+// rows, hwords >= ceil(V / 32); pslots int32 [B] the row's history row (< 0 or
+// >= n_slots: not penalised); prows (optional) int32 [n_rows] one flag per
+// mask row (row b's own index without mask_idx), 0 = not penalised.
+int dmcp_masked_penal(const void* logits, const void* mask, const void* mask_idx, int n_masks, void* ids, int B,
+                      int V, int ld, const void* slots, const void* positions, unsigned seed, float inv_temperature,
+                      const void* history, int hwords, int n_slots, const void* pslots, const void* prows, int n_rows,
+                      float theta, float inv_theta, float alpha, void* stream) {
+    if (B <= 0) return 0;
+    const bool sample = inv_temperature != 0.f;
+    if (!logits || !ids || V <= 0 || V > ld || (mask_idx && (!mask || n_masks <= 0)) ||
+        (sample && (!slots || !positions || !(inv_temperature > 0.f))) || !history || !pslots ||
+        hwords < (V + 31) / 32 || n_slots <= 0 || (prows && n_rows < (mask_idx ? n_masks : B)) || !(theta > 0.f) ||
+        !(inv_theta > 0.f) || !(alpha == alpha))
+        return hipErrorInvalidValue;
+    const bool vec = (ld % 8 == 0) && (reinterpret_cast<uintptr_t>(logits) % 16 == 0);
+    const PenaltyKeys pk{(const uint32_t*)history, (const int32_t*)pslots, (const int32_t*)prows, hwords, n_slots,
+                         n_rows, theta, inv_theta, alpha};
+    if (sample) {
+        const SampleKeys sk{(const int32_t*)slots, (const int32_t*)positions, seed, inv_temperature};
+        masked_argmax_kernel<true, true><<<B, MA_T, 0, (hipStream_t)stream>>>(
+            (const uint16_t*)logits, (const uint32_t*)mask, (const int32_t*)mask_idx, n_masks, (int32_t*)ids, V, ld,
+            vec ? V / 8 : 0, sk, pk);
+    } else {
+        masked_argmax_kernel<false, true><<<B, MA_T, 0, (hipStream_t)stream>>>(
+            (const uint16_t*)logits, (const uint32_t*)mask, (const int32_t*)mask_idx, n_masks, (int32_t*)ids, V, ld,
+            vec ? V / 8 : 0, NoSampleKeys{}, pk);
+    }
+    return hipGetLastError();
+}
+
+// history[slots[r]] |= bit of row r's token (history_mark_kernel): tokens /
+// slots int32 [rows]; src (optional) int32 [rows] with last_ids int32 [n_last];
+// exempt (optional) uint32 [hwords] ids never recorded; V <= 32 * hwords.
+int dmcp_history_mark(void* history, int hwords, int n_slots, const void* tokens, const void* slots, const void* src,
+                      const void* last_ids, int n_last, const void* exempt, int rows, int V, void* stream) {
+    if (rows <= 0) return 0;
+    if (!history || !tokens || !slots || hwords <= 0 || n_slots <= 0 || V <= 0 || V > 32 * (long)hwords ||
+        (src && (!last_ids || n_last <= 0)))
+        return hipErrorInvalidValue;
+    history_mark_kernel<<<(rows + kBlock - 1) / kBlock, kBlock, 0, (hipStream_t)stream>>>(
+        (uint32_t*)history, hwords, n_slots, (const int32_t*)tokens, (const int32_t*)slots, (const int32_t*)src,
+        (const int32_t*)last_ids, n_last, (const uint32_t*)exempt, rows, V);
+    return hipGetLastError();
+}
+
+// zero the history rows of the n slots of a HOST array (entries outside
+// [0, n_slots) are ignored); queued on the stream, nothing is copied or awaited
+int dmcp_history_reset(void* history, int hwords, int n_slots, const int* host_slots, int n, void* stream) {
+    if (n <= 0) return 0;
+    if (!history || !host_slots || hwords <= 0 || n_slots <= 0) return hipErrorInvalidValue;
+    for (int i = 0; i < n; i += HR_MAX) {
+        HistorySlots hs;
+        const int k = n - i < HR_MAX ? n - i : HR_MAX;
+        for (int j = 0; j < HR_MAX; ++j) hs.s[j] = j < k ? host_slots[i + j] : -1;
+        history_reset_kernel<<<dim3((hwords + kBlock - 1) / kBlock, k), kBlock, 0, (hipStream_t)stream>>>(
+            (uint32_t*)history, hwords, n_slots, hs);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return 0;
 }
 
 // dmcp_masked_argmax at a temperature: ids[b] = argmax over the allowed v of
@@ -1140,7 +1269,7 @@ int dmcp_masked_sample(const void* logits, const void* mask, const void* mask_id
     const SampleKeys sk{(const int32_t*)slots, (const int32_t*)positions, seed, inv_temperature};
     masked_argmax_kernel<true><<<B, MA_T, 0, (hipStream_t)stream>>>(
         (const uint16_t*)logits, (const uint32_t*)mask, (const int32_t*)mask_idx, n_masks, (int32_t*)ids, V, ld,
-        vec ? V / 8 : 0, sk);
+        vec ? V / 8 : 0, sk, NoPenaltyKeys{});
     return hipGetLastError();
 }
 

@@ -89,11 +89,12 @@ __device__ __forceinline__ int tslot(int j, int r) { return j ^ (r & 7); }
 // Measured slower and removed (git history has the code): an L2 prefetch of
 // the weight stream, 32-deep stages, a 2-stage ring cap and a register-weight
 // kernel (profiles/tgemm_l2_prefetch_ab_r5.jsonl, profiles/tgemm_regweights_ab_r5.jsonl).
-template <int XT, int MODE, int PROBE = 0>
+template <int XT, int MODE, int PROBE = 0, bool PENAL = false>
 __global__ __launch_bounds__(TTH) __attribute__((amdgpu_waves_per_eu(2, 2))) void tgemm_kernel(
     const uint16_t* __restrict__ x, const uint16_t* __restrict__ w, uint16_t* __restrict__ y, float* __restrict__ part,
     int M, int N, int K, int cps, int S, int ntiles, int mparts, int mrows, int I, const uint32_t* __restrict__ masks,
-    const int32_t* __restrict__ midx, int n_masks, int wwords, sample_keys_t<MODE == TM_SAMPLE> sk) {
+    const int32_t* __restrict__ midx, int n_masks, int wwords, sample_keys_t<MODE == TM_SAMPLE> sk,
+    penalty_keys_t<PENAL> pk) {
     constexpr int NF = TNB / 64;       // A fragments per wave (16 weight rows each): a quarter of the tile's rows
     constexpr int RCH = TKC / 8;       // 16-B chunks per image row
     constexpr int PR = 64 / RCH;       // image rows per 1-KiB LDS-DMA piece
@@ -282,14 +283,25 @@ __global__ __launch_bounds__(TTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 int mr = midx ? midx[m] : 0;
                 mr = mr < 0 ? 0 : (mr >= n_masks ? n_masks - 1 : mr);
                 const uint32_t* mrow = masks + (size_t)mr * wwords + (c0 >> 5);
+                // PENAL: the row's history word beside its mask word (wgemm.hip)
+                [[maybe_unused]] const uint32_t* hrow = nullptr;
+                if constexpr (PENAL) {
+                    hrow = penalty_row(pk, m, mr);
+                    if (hrow) hrow += c0 >> 5;
+                }
 #pragma unroll
                 for (int f = 0; f < NF; ++f) {
                     const uint32_t word = mrow[(16 * f + 4 * g) >> 5];
+                    [[maybe_unused]] uint32_t hword = 0u;
+                    if constexpr (PENAL) hword = hrow ? hrow[(16 * f + 4 * g) >> 5] : 0u;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int c = 16 * f + 4 * g + i;
                         if ((word >> (c & 31)) & 1u) {
                             float v = bf2f(f2bf(acc[f][t][i]));
+                            if constexpr (PENAL) {
+                                if ((hword >> (c & 31)) & 1u) v = penalize(v, pk.theta, pk.inv_theta, pk.alpha);
+                            }
                             if constexpr (MODE == TM_SAMPLE) v = gumbel_score(v, sk.inv_t, key, c0 + c);
                             if (v > bv) { bv = v; bi = c0 + c; }  // columns ascend: strict > keeps the lowest
                         }
@@ -335,11 +347,12 @@ __global__ __launch_bounds__(TTH) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 }
 
-template <int MODE, int PROBE = 0>
+template <int MODE, int PROBE = 0, bool PENAL = false>
 hipError_t launch_tgemm(const uint16_t* x, const uint16_t* w, uint16_t* y, float* part, int M, int N, int K, int S,
                         int mparts, int I, hipStream_t st, const uint32_t* masks, const int32_t* midx, int n_masks,
-                        int wwords, const SampleKeys& sk = SampleKeys{}) {
+                        int wwords, const SampleKeys& sk = SampleKeys{}, const PenaltyKeys& pk = PenaltyKeys{}) {
     const auto keys = pick_keys<MODE == TM_SAMPLE>(sk);
+    const auto pen = pick_penalty<PENAL>(pk);
     const int ntiles = (MODE == TM_SWIGLU ? 2 * I : N) / TNB;
     const int mrows = (((M + mparts - 1) / mparts) + 15) & ~15;
     // staged X rows in 32-row steps (>= 64)
@@ -349,8 +362,8 @@ hipError_t launch_tgemm(const uint16_t* x, const uint16_t* w, uint16_t* y, float
     const int cps = (chunks + S - 1) / S;
     const dim3 grid((unsigned)(ntiles * S * mparts));
 #define DMCP_TG(XT)                                                                                          \
-    tgemm_kernel<XT, MODE, PROBE><<<grid, TTH, 0, st>>>(x, w, y, part, M, N, K, cps, S, ntiles, mparts, mrows, I, \
-                                                        masks, midx, n_masks, wwords, keys)
+    tgemm_kernel<XT, MODE, PROBE, PENAL><<<grid, TTH, 0, st>>>(x, w, y, part, M, N, K, cps, S, ntiles, mparts,   \
+                                                               mrows, I, masks, midx, n_masks, wwords, keys, pen)
     switch (xt) {
         case 2: DMCP_TG(2); break;
         case 3: DMCP_TG(3); break;
@@ -427,6 +440,42 @@ int dmcp_tgemm_sample(const void* x, const void* w, void* part, int M, int N, in
     hipError_t e = launch_tgemm<TM_SAMPLE>((const uint16_t*)x, (const uint16_t*)w, nullptr, (float*)part, M, N, K, 1,
                                            mparts, 0, st, (const uint32_t*)masks, (const int32_t*)midx, n_masks,
                                            wwords, sk);
+    if (e != hipSuccess) return e;
+    argmax_pairs_kernel<<<(M + kBlock / kWave - 1) / (kBlock / kWave), kBlock, 0, st>>>(
+        (const float2*)part, 4 * (N / TNB), M, (int32_t*)ids);
+    return hipGetLastError();
+}
+
+// mode 3 (inv_temperature == 0; slots / positions / seed unused) or
+// dmcp_tgemm_sample (inv_temperature > 0) under a repetition / presence
+// penalty: the penalty arguments of dmcp_masked_penal (dmcp_kernels.hip), the
+// flags indexed by the mask row.  Same contract, workspace and pair reduction.
+int dmcp_tgemm_penal(const void* x, const void* w, void* part, int M, int N, int K, int mparts, const void* masks,
+                     const void* midx, int n_masks, int wwords, void* ids, const void* slots, const void* positions,
+                     unsigned seed, float inv_temperature, const void* history, int hwords, int n_slots,
+                     const void* pslots, const void* prows, int n_rows, float theta, float inv_theta, float alpha,
+                     void* stream) {
+    if (M <= 0) return 0;
+    const bool sample = inv_temperature != 0.f;
+    if (!x || !w || mparts < 1 || K <= 0 || K % TKC != 0 || (((M + mparts - 1) / mparts + 15) & ~15) > 256 ||
+        N <= 0 || N % TNB != 0 || !part || !masks || !ids || n_masks < 1 || wwords < (N + 31) / 32 ||
+        (sample && (!slots || !positions || !(inv_temperature > 0.f))) || !history || !pslots ||
+        hwords < (N + 31) / 32 || n_slots <= 0 || (prows && n_rows < n_masks) || !(theta > 0.f) ||
+        !(inv_theta > 0.f) || !(alpha == alpha))
+        return hipErrorInvalidValue;
+    auto st = (hipStream_t)stream;
+    const SampleKeys sk{(const int32_t*)slots, (const int32_t*)positions, seed, inv_temperature};
+    const PenaltyKeys pk{(const uint32_t*)history, (const int32_t*)pslots, (const int32_t*)prows, hwords, n_slots,
+                         n_rows, theta, inv_theta, alpha};
+    hipError_t e;
+    if (sample)
+        e = launch_tgemm<TM_SAMPLE, 0, true>((const uint16_t*)x, (const uint16_t*)w, nullptr, (float*)part, M, N, K, 1,
+                                             mparts, 0, st, (const uint32_t*)masks, (const int32_t*)midx, n_masks,
+                                             wwords, sk, pk);
+    else
+        e = launch_tgemm<TM_ARGMAX, 0, true>((const uint16_t*)x, (const uint16_t*)w, nullptr, (float*)part, M, N, K, 1,
+                                             mparts, 0, st, (const uint32_t*)masks, (const int32_t*)midx, n_masks,
+                                             wwords, sk, pk);
     if (e != hipSuccess) return e;
     argmax_pairs_kernel<<<(M + kBlock / kWave - 1) / (kBlock / kWave), kBlock, 0, st>>>(
         (const float2*)part, 4 * (N / TNB), M, (int32_t*)ids);

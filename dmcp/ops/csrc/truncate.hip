@@ -58,21 +58,48 @@ __device__ __forceinline__ uint32_t key_bits(uint32_t key) {
 }
 __device__ __forceinline__ float key_value(uint32_t key) { return __uint_as_float(key_bits(key) << 16); }
 
+// The PENAL variant's view of a row (repetition / presence penalty,
+// dmcp_common.hpp penalize): every pass maps a loaded value whose history
+// bit is set through the penalty BEFORE keying it, so the radix passes, the
+// thresholds and the reported tau are those of the penalised values.  The
+// history byte of an 8-id chunk travels with its mask byte.  hrow is null for
+// a row that is not penalised; the plain variant carries nothing.
+struct RowPenalty {
+    const uint32_t* hrow;
+    float theta, inv_theta, alpha;
+};
+struct NoRowPenalty {};
+template <bool PENAL>
+using row_penalty_t = std::conditional_t<PENAL, RowPenalty, NoRowPenalty>;
+
 // f(key, id) for every id of the row that the mask allows
-template <class F>
+template <bool PENAL, class F>
 __device__ __forceinline__ void for_allowed(const uint16_t* __restrict__ row, const uint32_t* __restrict__ mrow,
-                                            int V, int nch, F&& f) {
+                                            int V, int nch, const row_penalty_t<PENAL>& rp, F&& f) {
     for (int c = threadIdx.x; c < nch; c += TS_T) {
         const uint4 q = *reinterpret_cast<const uint4*>(row + (size_t)c * 8);
         const uint32_t m = mrow ? (mrow[c >> 2] >> ((c & 3) * 8)) & 0xFFu : 0xFFu;
+        [[maybe_unused]] uint32_t h = 0u;
+        if constexpr (PENAL) h = rp.hrow ? (rp.hrow[c >> 2] >> ((c & 3) * 8)) & 0xFFu : 0u;
         const uint32_t w[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-            if ((m >> j) & 1u) f(bf_key((j & 1) ? (w[j >> 1] >> 16) : (w[j >> 1] & 0xFFFFu)), c * 8 + j);
+            if ((m >> j) & 1u) {
+                uint32_t bits = (j & 1) ? (w[j >> 1] >> 16) : (w[j >> 1] & 0xFFFFu);
+                if constexpr (PENAL) {
+                    if ((h >> j) & 1u) bits = f2bf(penalize(bf2f((uint16_t)bits), rp.theta, rp.inv_theta, rp.alpha));
+                }
+                f(bf_key(bits), c * 8 + j);
+            }
     }
     for (int v = nch * 8 + threadIdx.x; v < V; v += TS_T) {
         if (mrow && !((mrow[v >> 5] >> (v & 31)) & 1u)) continue;
-        f(bf_key(row[v]), v);
+        uint32_t bits = row[v];
+        if constexpr (PENAL) {
+            if (rp.hrow && ((rp.hrow[v >> 5] >> (v & 31)) & 1u))
+                bits = f2bf(penalize(bf2f((uint16_t)bits), rp.theta, rp.inv_theta, rp.alpha));
+        }
+        f(bf_key(bits), v);
     }
 }
 
@@ -119,14 +146,15 @@ __device__ __forceinline__ void block_totals(int (&cnt)[16], float (&wsum)[16], 
 // One radix pass: the counts (and weights) per 4-bit digit at `shift` of the
 // allowed ids whose key is >= floor_key and whose bits above the digit equal
 // `prefix`.
-template <bool WEIGHTS>
+template <bool WEIGHTS, bool PENAL>
 __device__ __forceinline__ void digit_pass(const uint16_t* __restrict__ row, const uint32_t* __restrict__ mrow, int V,
-                                           int nch, int shift, uint32_t prefix, uint32_t floor_key, float x_max,
+                                           int nch, const row_penalty_t<PENAL>& rp, int shift, uint32_t prefix,
+                                           uint32_t floor_key, float x_max,
                                            float inv_t, int (&cnt)[16], float (&wsum)[16], int (*red_c)[16],
                                            float (*red_w)[16], int* tot_c, float* tot_w) {
 #pragma unroll
     for (int j = 0; j < 16; ++j) { cnt[j] = 0; wsum[j] = 0.f; }
-    for_allowed(row, mrow, V, nch, [&](uint32_t key, int) {
+    for_allowed<PENAL>(row, mrow, V, nch, rp, [&](uint32_t key, int) {
         if ((key >> (shift + 4)) != prefix || key < floor_key) return;
         const uint32_t d = (key >> shift) & 15u;
         float w = 0.f;
@@ -141,10 +169,11 @@ __device__ __forceinline__ void digit_pass(const uint16_t* __restrict__ row, con
     block_totals<WEIGHTS>(cnt, wsum, red_c, red_w, tot_c, tot_w);
 }
 
+template <bool PENAL>
 __global__ __launch_bounds__(TS_T) void truncated_sample_kernel(
     const uint16_t* __restrict__ logits, const uint32_t* __restrict__ mask, const int32_t* __restrict__ mask_idx,
     int n_masks, int32_t* __restrict__ ids, int V, int ld, int nch, SampleKeys sk, int top_k, float top_p,
-    float ln_min_p, int32_t* __restrict__ stats) {
+    float ln_min_p, int32_t* __restrict__ stats, penalty_keys_t<PENAL> pk) {
     __shared__ int red_c[TS_W][16];
     __shared__ float red_w[TS_W][16];
     __shared__ int tot_c[16];
@@ -171,11 +200,13 @@ __global__ __launch_bounds__(TS_T) void truncated_sample_kernel(
         mr = mr < 0 ? 0 : (mr >= n_masks ? n_masks - 1 : mr);
     }
     const uint32_t* mrow = mask ? mask + (size_t)mr * ((V + 31) >> 5) : nullptr;
+    row_penalty_t<PENAL> rp;
+    if constexpr (PENAL) rp = RowPenalty{penalty_row(pk, b, mr), pk.theta, pk.inv_theta, pk.alpha};
 
     // pass 0: x_max (as a key) and |A|
     uint32_t kmax = 0;
     int n_allowed = 0;
-    for_allowed(row, mrow, V, nch, [&](uint32_t key, int) {
+    for_allowed<PENAL>(row, mrow, V, nch, rp, [&](uint32_t key, int) {
         kmax = key > kmax ? key : kmax;
         ++n_allowed;
     });
@@ -213,8 +244,8 @@ __global__ __launch_bounds__(TS_T) void truncated_sample_kernel(
         uint32_t prefix = 0;
         int need = top_k;  // the need-th largest among the ids under the prefix
         for (int shift = 12; shift >= 0; shift -= 4) {
-            digit_pass<false>(row, mrow, V, nch, shift, prefix, 0u, x_max, inv_t, cnt, wsum, red_c, red_w, tot_c,
-                              tot_w);
+            digit_pass<false, PENAL>(row, mrow, V, nch, rp, shift, prefix, 0u, x_max, inv_t, cnt, wsum, red_c, red_w,
+                                     tot_c, tot_w);
             int pick = 0;
             bool found = false;
 #pragma unroll
@@ -232,8 +263,8 @@ __global__ __launch_bounds__(TS_T) void truncated_sample_kernel(
         uint32_t prefix = 0;
         float above = 0.f, target = 0.f;  // the weight above the prefix's range; p * Z
         for (int shift = 12; shift >= 0; shift -= 4) {
-            digit_pass<true>(row, mrow, V, nch, shift, prefix, tkey, x_max, inv_t, cnt, wsum, red_c, red_w, tot_c,
-                             tot_w);
+            digit_pass<true, PENAL>(row, mrow, V, nch, rp, shift, prefix, tkey, x_max, inv_t, cnt, wsum, red_c, red_w,
+                                    tot_c, tot_w);
             if (shift == 12) {  // every survivor is in one of the 16 ranges: their total is Z
                 float z = 0.f;
 #pragma unroll
@@ -269,7 +300,7 @@ __global__ __launch_bounds__(TS_T) void truncated_sample_kernel(
     float best = -INFINITY;
     int bi = 0x7fffffff, kept = 0;
     uint32_t kmin = 0xFFFFu;
-    for_allowed(row, mrow, V, nch, [&](uint32_t key, int v) {
+    for_allowed<PENAL>(row, mrow, V, nch, rp, [&](uint32_t key, int v) {
         if (key < tkey) return;
         const float x = key_value(key);
         if (cut_m && !((x - x_max) * inv_t >= ln_min_p)) return;
@@ -328,9 +359,33 @@ int dmcp_truncated_sample(const void* logits, const void* mask, const void* mask
     // whole 16-B chunks only when every row start is 16-B aligned
     const bool vec = (ld % 8 == 0) && (reinterpret_cast<uintptr_t>(logits) % 16 == 0);
     const SampleKeys sk{(const int32_t*)slots, (const int32_t*)positions, seed, inv_temperature};
-    truncated_sample_kernel<<<B, TS_T, 0, (hipStream_t)stream>>>(
+    truncated_sample_kernel<false><<<B, TS_T, 0, (hipStream_t)stream>>>(
         (const uint16_t*)logits, (const uint32_t*)mask, (const int32_t*)mask_idx, n_masks, (int32_t*)ids, V, ld,
-        vec ? V / 8 : 0, sk, top_k, top_p, ln_min_p, (int32_t*)stats);
+        vec ? V / 8 : 0, sk, top_k, top_p, ln_min_p, (int32_t*)stats, NoPenaltyKeys{});
+    return hipGetLastError();
+}
+
+// dmcp_truncated_sample under a repetition / presence penalty: the penalty
+// arguments of dmcp_masked_penal (dmcp_kernels.hip); thresholds, tau and the
+// kept count are those of the penalised values.
+int dmcp_truncated_penal(const void* logits, const void* mask, const void* mask_idx, int n_masks, void* ids, int B,
+                         int V, int ld, const void* slots, const void* positions, unsigned seed,
+                         float inv_temperature, int top_k, float top_p, float ln_min_p, void* stats,
+                         const void* history, int hwords, int n_slots, const void* pslots, const void* prows,
+                         int n_rows, float theta, float inv_theta, float alpha, void* stream) {
+    if (B <= 0) return 0;
+    if (!logits || !ids || V <= 0 || V > ld || (mask_idx && (!mask || n_masks <= 0)) || !slots || !positions ||
+        !(inv_temperature > 0.f) || top_k < 0 || !(top_p > 0.f && top_p <= 1.f) || !(ln_min_p < 0.f) || !history ||
+        !pslots || hwords < (V + 31) / 32 || n_slots <= 0 || (prows && n_rows < (mask_idx ? n_masks : B)) ||
+        !(theta > 0.f) || !(inv_theta > 0.f) || !(alpha == alpha))
+        return hipErrorInvalidValue;
+    const bool vec = (ld % 8 == 0) && (reinterpret_cast<uintptr_t>(logits) % 16 == 0);
+    const SampleKeys sk{(const int32_t*)slots, (const int32_t*)positions, seed, inv_temperature};
+    const PenaltyKeys pk{(const uint32_t*)history, (const int32_t*)pslots, (const int32_t*)prows, hwords, n_slots,
+                         n_rows, theta, inv_theta, alpha};
+    truncated_sample_kernel<true><<<B, TS_T, 0, (hipStream_t)stream>>>(
+        (const uint16_t*)logits, (const uint32_t*)mask, (const int32_t*)mask_idx, n_masks, (int32_t*)ids, V, ld,
+        vec ? V / 8 : 0, sk, top_k, top_p, ln_min_p, (int32_t*)stats, pk);
     return hipGetLastError();
 }
 

@@ -44,7 +44,13 @@
 //     read back per step by F.linear + masked_argmax);
 //   * MODE_SAMPLE is MODE_ARGMAX at a temperature: the same tiles and pairs,
 //     each allowed id's value perturbed in the epilogue with Gumbel noise
-//     (dmcp_common.hpp gumbel_score) keyed by the row's slot and position.
+//     (dmcp_common.hpp gumbel_score) keyed by the row's slot and position;
+//   * PENAL (either selection mode): the repetition / presence penalty
+//     (dmcp_common.hpp penalize).  The row's history word is read where its
+//     mask word is -- history + slot * hwords + (n0 >> 5), once per row and
+//     32 ids -- and an allowed id whose bit is set competes with its
+//     penalised value (before the noise); ids the grammar excludes cost
+//     nothing more.
 #include "dmcp_common.hpp"
 
 namespace {
@@ -52,13 +58,14 @@ namespace {
 constexpr int kKC = 64;  // K per LDS stage
 constexpr int MODE_BF16 = 0, MODE_PART = 1, MODE_SWIGLU = 2, MODE_ARGMAX = 3, MODE_SAMPLE = 4;
 
-template <int NB, int MT, int MR, int MODE, int ST, int AUXW = 0>
+template <int NB, int MT, int MR, int MODE, int ST, int AUXW = 0, bool PENAL = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) void wgemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
                                                        uint16_t* __restrict__ y, float* __restrict__ part, int M, int N,
                                                        int K, int ks, int S, int ntiles, int mparts, int mrows,
                                                        int I, const uint32_t* __restrict__ masks,
                                                        const int32_t* __restrict__ midx, int n_masks, int wwords,
-                                                       sample_keys_t<MODE == MODE_SAMPLE> sk) {
+                                                       sample_keys_t<MODE == MODE_SAMPLE> sk,
+                                                       penalty_keys_t<PENAL> pk) {
     constexpr int NF = NB / 16;         // A fragments (16 weight rows each)
     // X rows staged per block (a multiple of 32, <= 4 waves x MT 16-row
     // tiles): the M part rounded up to 32 rows, not to 64 -- at 320 rows
@@ -246,14 +253,24 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
                 int mr = midx ? midx[m] : 0;
                 mr = mr < 0 ? 0 : (mr >= n_masks ? n_masks - 1 : mr);
                 const uint32_t* mrow = masks + (size_t)mr * wwords + (n0 >> 5);
+                [[maybe_unused]] const uint32_t* hrow = nullptr;
+                if constexpr (PENAL) {
+                    hrow = penalty_row(pk, m, mr);
+                    if (hrow) hrow += n0 >> 5;
+                }
 #pragma unroll
                 for (int f = 0; f < NF; ++f) {
                     const uint32_t word = mrow[(16 * f + 4 * g) >> 5];
+                    [[maybe_unused]] uint32_t hword = 0u;
+                    if constexpr (PENAL) hword = hrow ? hrow[(16 * f + 4 * g) >> 5] : 0u;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int c = 16 * f + 4 * g + i;
                         if ((word >> (c & 31)) & 1u) {
                             float x = bf2f(f2bf(acc[f][t][i]));
+                            if constexpr (PENAL) {
+                                if ((hword >> (c & 31)) & 1u) x = penalize(x, pk.theta, pk.inv_theta, pk.alpha);
+                            }
                             if constexpr (MODE == MODE_SAMPLE) x = gumbel_score(x, sk.inv_t, key, n0 + c);
                             if (x > bv) { bv = x; bi = n0 + c; }  // columns ascend: strict > keeps the lowest
                         }
@@ -302,12 +319,13 @@ constexpr int kStages = 3;  // LDS ring stages (2 in flight while one is compute
 // dmcp_wgemm_set_aux: the weight stream's cache policy (0 default, 2 nt)
 int g_wgemm_auxw = 0;
 
-template <int NB, int MODE>
+template <int NB, int MODE, bool PENAL = false>
 hipError_t launch_wgemm(const uint16_t* x, const uint16_t* w, uint16_t* y, float* part, int M, int N, int K, int S,
                         int mparts, int I, hipStream_t st, const uint32_t* masks = nullptr,
                         const int32_t* midx = nullptr, int n_masks = 0, int wwords = 0,
-                        const SampleKeys& sk = SampleKeys{}) {
+                        const SampleKeys& sk = SampleKeys{}, const PenaltyKeys& pk = PenaltyKeys{}) {
     const auto keys = pick_keys<MODE == MODE_SAMPLE>(sk);
+    const auto pen = pick_penalty<PENAL>(pk);
     const int ntiles = (MODE == MODE_SWIGLU ? 2 * I : N) / NB;
     const int mrows = (((M + mparts - 1) / mparts) + 15) & ~15;
     const int mt = (mrows + 4 * 16 - 1) / (4 * 16);  // 16-row tiles per wave
@@ -317,11 +335,13 @@ hipError_t launch_wgemm(const uint16_t* x, const uint16_t* w, uint16_t* y, float
 #define DMCP_WG1(MT, MR)                                                                                        \
     do {                                                                                                        \
         if (g_wgemm_auxw == 2)                                                                                  \
-            wgemm_kernel<NB, MT, MR, MODE, kStages, 2><<<grid, kBlock, 0, st>>>(                                \
-                x, w, y, part, M, N, K, ks, S, ntiles, mparts, mrows, I, masks, midx, n_masks, wwords, keys);   \
+            wgemm_kernel<NB, MT, MR, MODE, kStages, 2, PENAL><<<grid, kBlock, 0, st>>>(                         \
+                x, w, y, part, M, N, K, ks, S, ntiles, mparts, mrows, I, masks, midx, n_masks, wwords, keys,    \
+                pen);                                                                                           \
         else                                                                                                    \
-            wgemm_kernel<NB, MT, MR, MODE, kStages><<<grid, kBlock, 0, st>>>(                                   \
-                x, w, y, part, M, N, K, ks, S, ntiles, mparts, mrows, I, masks, midx, n_masks, wwords, keys);   \
+            wgemm_kernel<NB, MT, MR, MODE, kStages, 0, PENAL><<<grid, kBlock, 0, st>>>(                         \
+                x, w, y, part, M, N, K, ks, S, ntiles, mparts, mrows, I, masks, midx, n_masks, wwords, keys,    \
+                pen);                                                                                           \
     } while (0)
 #define DMCP_WG(MT)                  \
     do {                             \
@@ -447,6 +467,53 @@ int dmcp_lm_head_sample(const void* x, const void* w, const void* masks, const v
     if (e != hipSuccess) return e;
     argmax_pairs_kernel<<<(M + kBlock / kWave - 1) / (kBlock / kWave), kBlock, 0, st>>>(
         (const float2*)best, ntiles, M, (int32_t*)ids);
+    return hipGetLastError();
+}
+
+// dmcp_lm_head_argmax (inv_temperature == 0; slots / positions / seed unused)
+// or dmcp_lm_head_sample (inv_temperature > 0) under a repetition / presence
+// penalty: the penalty arguments of dmcp_masked_penal (dmcp_kernels.hip), the
+// flags indexed by the mask row.  Same contract, tiles, workspace and pair
+// reduction as the unpenalised entry points.
+int dmcp_lm_head_penal(const void* x, const void* w, const void* masks, const void* midx, int n_masks, int wwords,
+                       void* best, void* ids, int M, int V, int K, int mparts, const void* slots,
+                       const void* positions, unsigned seed, float inv_temperature, const void* history, int hwords,
+                       int n_slots, const void* pslots, const void* prows, int n_rows, float theta, float inv_theta,
+                       float alpha, void* stream) {
+    if (M <= 0) return 0;
+    const bool sample = inv_temperature != 0.f;
+    if (!x || !w || !masks || !best || !ids || M > 512 || n_masks < 1 || wwords < (V + 31) / 32 || mparts < 1 ||
+        K % kKC != 0 || V <= 0 || V % 64 != 0 || (((M + mparts - 1) / mparts + 15) & ~15) > 256 ||
+        (sample && (!slots || !positions || !(inv_temperature > 0.f))) || !history || !pslots ||
+        hwords < (V + 31) / 32 || n_slots <= 0 || (prows && n_rows < n_masks) || !(theta > 0.f) ||
+        !(inv_theta > 0.f) || !(alpha == alpha))
+        return hipErrorInvalidValue;
+    auto st = (hipStream_t)stream;
+    auto xx = (const uint16_t*)x;
+    auto ww = (const uint16_t*)w;
+    auto bb = (float*)best;
+    auto mk = (const uint32_t*)masks;
+    auto mi = (const int32_t*)midx;
+    const SampleKeys sk{(const int32_t*)slots, (const int32_t*)positions, seed, inv_temperature};
+    const PenaltyKeys pk{(const uint32_t*)history, (const int32_t*)pslots, (const int32_t*)prows, hwords, n_slots,
+                         n_rows, theta, inv_theta, alpha};
+    hipError_t e;
+    const int nb = V % 128 == 0 ? 128 : 64;
+    if (nb == 128 && sample)
+        e = launch_wgemm<128, MODE_SAMPLE, true>(xx, ww, nullptr, bb, M, V, K, 1, mparts, 0, st, mk, mi, n_masks,
+                                                 wwords, sk, pk);
+    else if (nb == 128)
+        e = launch_wgemm<128, MODE_ARGMAX, true>(xx, ww, nullptr, bb, M, V, K, 1, mparts, 0, st, mk, mi, n_masks,
+                                                 wwords, sk, pk);
+    else if (sample)
+        e = launch_wgemm<64, MODE_SAMPLE, true>(xx, ww, nullptr, bb, M, V, K, 1, mparts, 0, st, mk, mi, n_masks,
+                                                wwords, sk, pk);
+    else
+        e = launch_wgemm<64, MODE_ARGMAX, true>(xx, ww, nullptr, bb, M, V, K, 1, mparts, 0, st, mk, mi, n_masks,
+                                                wwords, sk, pk);
+    if (e != hipSuccess) return e;
+    argmax_pairs_kernel<<<(M + kBlock / kWave - 1) / (kBlock / kWave), kBlock, 0, st>>>(
+        (const float2*)best, V / nb, M, (int32_t*)ids);
     return hipGetLastError();
 }
 

@@ -31,6 +31,7 @@ _i = ctypes.c_int
 _f = ctypes.c_float
 _u = ctypes.c_uint
 ABI_VERSION = 20  # must match dmcp_abi_version() in csrc/dmcp_kernels.hip
+_PEN = [_vp, _i, _i, _vp, _vp, _i, _f, _f, _f]  # the penalty arguments of the *_penal entry points
 
 
 class HipOpsError(RuntimeError):
@@ -105,6 +106,20 @@ def lib() -> ctypes.CDLL:
             # dmcp_masked_sample's list + top_k, top_p, fp32(log(min_p)), stats (ahead of the stream)
             "dmcp_truncated_sample": ([_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _u, _f, _i, _f, _f, _vp, _vp],
                                       _i),
+            # the selection entry points under a repetition / presence penalty: their sampling siblings' lists
+            # (1 / temperature 0 = greedy) + _PEN: history, words per row, n_slots, slots, rows flags, n_rows,
+            # theta, fp32(1 / theta), alpha (ahead of the stream)
+            "dmcp_masked_penal": ([_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _u, _f] + _PEN + [_vp], _i),
+            "dmcp_lm_head_penal": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _u, _f] + _PEN
+                                   + [_vp], _i),
+            "dmcp_tgemm_penal": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _u, _f] + _PEN
+                                 + [_vp], _i),
+            "dmcp_truncated_penal": ([_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _u, _f, _i, _f, _f, _vp] + _PEN
+                                     + [_vp], _i),
+            # history, words per row, n_slots, tokens, slots, src, last_ids, n_last, exempt, rows, vocab
+            "dmcp_history_mark": ([_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp], _i),
+            # history, words per row, n_slots, host int array of slots, its length
+            "dmcp_history_reset": ([_vp, _i, _i, _vp, _i, _vp], _i),
         }
         for name, (args, res) in sigs.items():
             try:
@@ -562,11 +577,113 @@ def silu_mul(gate_up: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch
     return out
 
 
+Penalty = reference.Penalty  # the repetition / presence penalty of a selection call (definitions: reference.py)
+
+
+def _req_penalty(penalty: Optional[Penalty], name: str, rows: int, W: int, n_rows: int,
+                 device=None) -> Optional[tuple]:
+    """The ``penalty`` argument of the selection ops, checked before any
+    launch (a HipOpsError names the argument).  None when there is nothing to
+    apply (no penalty, or theta 1 and alpha 0: the caller takes its existing
+    entry point); else (history, n_slots, slots, rows flags, n_rows, theta,
+    fp32(1 / theta), alpha).  history, slots and rows must be on ``device``
+    (the selection's input).  The slot values are read back and checked
+    against the table unless the penalty says ``check_slots=False`` or the
+    stream is capturing (the kernels skip a slot outside the table either
+    way)."""
+    if penalty is None:
+        return None
+    if not isinstance(penalty, Penalty):
+        raise HipOpsError(f"{name}: penalty must be an ops.Penalty, got {type(penalty).__name__}")
+    sl = penalty.slots
+    values = not (isinstance(sl, torch.Tensor) and sl.is_cuda and torch.cuda.is_current_stream_capturing())
+    try:
+        theta, inv_theta, alpha = penalty.check(name, rows, W, n_rows, values, device)
+    except ValueError as e:
+        raise HipOpsError(str(e)) from None
+    if penalty.off:
+        return None
+    _req(penalty.history, torch.int32, f"{name}.penalty.history")
+    _req(sl, torch.int32, f"{name}.penalty.slots")
+    if penalty.rows is not None:
+        _req(penalty.rows, torch.int32, f"{name}.penalty.rows")
+    return penalty.history, penalty.history.shape[0], sl, penalty.rows, n_rows, theta, inv_theta, alpha
+
+
+def _pen_args(pen: tuple, W: int, m0: int = 0) -> tuple:
+    """The _PEN arguments of a launch that starts at row ``m0`` of the call."""
+    history, n_slots, sl, rows, n_rows, theta, inv_theta, alpha = pen
+    return (_ptr(history), W, n_slots, _ptr(sl[m0:] if m0 else sl), _ptr(rows), n_rows if rows is not None else 0,
+            theta, inv_theta, alpha)
+
+
+def history_mark(history: torch.Tensor, tokens: torch.Tensor, slots: torch.Tensor,
+                 src: Optional[torch.Tensor] = None, last_ids: Optional[torch.Tensor] = None,
+                 exempt: Optional[torch.Tensor] = None, vocab: Optional[int] = None) -> torch.Tensor:
+    """Record the tokens a decode step feeds in the penalty's ``history``
+    (int32 [n_slots, W] bitset rows, in place): bit t of row ``slots[r]`` for
+    every row r whose slot is inside the table, t = ``last_ids[src[r]]`` where
+    ``src[r] >= 0`` else ``tokens[r]`` (the gather of :func:`decode_embed_norm`);
+    tokens outside [0, vocab) and the ids of the ``exempt`` bitset (int32 [W])
+    are not recorded.  One launch, integer atomics: capturable, reproducible."""
+    _req(history, torch.int32, "history_mark.history")
+    _req(tokens, torch.int32, "history_mark.tokens")
+    _req(slots, torch.int32, "history_mark.slots")
+    if history.dim() != 2 or history.shape[0] < 1:
+        raise HipOpsError(f"history_mark: history must be [n_slots, W], got {tuple(history.shape)}")
+    n_slots, W = history.shape
+    rows = tokens.numel()
+    V = 32 * W if vocab is None else int(vocab)
+    if not (0 < V <= 32 * W):
+        raise HipOpsError(f"history_mark: vocab {V} does not fit {W} words per row")
+    if slots.numel() != rows:
+        raise HipOpsError(f"history_mark: slots holds {slots.numel()} entries for {rows} rows")
+    n_last = 0
+    if src is not None:
+        _req(src, torch.int32, "history_mark.src")
+        if last_ids is None:
+            raise HipOpsError("history_mark: src given without last_ids")
+        _req(last_ids, torch.int32, "history_mark.last_ids")
+        n_last = last_ids.numel()
+        if src.numel() != rows or n_last < 1:
+            raise HipOpsError(f"history_mark: src {src.numel()} / last_ids {n_last} do not match {rows} rows")
+    if exempt is not None:
+        _req(exempt, torch.int32, "history_mark.exempt")
+        if exempt.numel() != W:
+            raise HipOpsError(f"history_mark: exempt must be int32 [{W}], got {tuple(exempt.shape)}")
+    _check(lib().dmcp_history_mark(_ptr(history), W, n_slots, _ptr(tokens), _ptr(slots), _ptr(src),
+                                   _ptr(last_ids if src is not None else None), n_last, _ptr(exempt), rows, V,
+                                   _stream()), "dmcp_history_mark")
+    return history
+
+
+def history_reset(history: torch.Tensor, slots) -> torch.Tensor:
+    """Zero the history rows of ``slots`` (a sequence of ints; entries outside
+    the table are ignored) on the current stream.  The slots travel as kernel
+    arguments: no index tensor, no copy, no synchronisation."""
+    _req(history, torch.int32, "history_reset.history")
+    if history.dim() != 2 or history.shape[0] < 1:
+        raise HipOpsError(f"history_reset: history must be [n_slots, W], got {tuple(history.shape)}")
+    try:
+        ids = [int(s) for s in slots]
+    except (TypeError, ValueError):
+        raise HipOpsError("history_reset: slots must be a sequence of ints") from None
+    if ids:
+        arr = (ctypes.c_int * len(ids))(*ids)
+        _check(lib().dmcp_history_reset(_ptr(history), history.shape[1], history.shape[0], arr, len(ids), _stream()),
+               "dmcp_history_reset")
+    return history
+
+
 def masked_argmax(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, vocab: Optional[int] = None,
-                  out: Optional[torch.Tensor] = None, mask_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None, mask_idx: Optional[torch.Tensor] = None,
+                  penalty: Optional[Penalty] = None) -> torch.Tensor:
     """logits [B, ld] bf16; mask int32 bitsets, ceil(V/32) words per row:
     [B, W] (row b -> mask b), or [M, W] with ``mask_idx`` int32 [B] choosing
-    a mask row per logits row.  None = all tokens allowed."""
+    a mask row per logits row.  None = all tokens allowed.  ``penalty``
+    (:class:`Penalty`): ids of the row's history compete with their penalised
+    value (:func:`dmcp.ops.reference.penalize`); None or (1, 0) is this
+    entry point unchanged."""
     _req(logits, torch.bfloat16, "masked_argmax.logits")
     B, ld = logits.shape
     V = vocab or ld
@@ -588,6 +705,12 @@ def masked_argmax(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, voc
         raise HipOpsError("masked_argmax: mask_idx given without a mask table")
     out = torch.empty((B,), dtype=torch.int32, device=logits.device) if out is None else out
     _req_out(out, torch.int32, B, "masked_argmax.out")
+    pen = _req_penalty(penalty, "masked_argmax", B, W, n_masks or B, logits.device)
+    if pen is not None:
+        _check(lib().dmcp_masked_penal(_ptr(logits), _ptr(mask), _ptr(mask_idx if mask is not None else None),
+                                       n_masks, _ptr(out), B, V, ld, _ptr(None), _ptr(None), 0, 0.0,
+                                       *_pen_args(pen, W), _stream()), "dmcp_masked_penal")
+        return out
     _check(lib().dmcp_masked_argmax(_ptr(logits), _ptr(mask), _ptr(mask_idx if mask is not None else None), n_masks,
                                     _ptr(out), B, V, ld, _stream()), "dmcp_masked_argmax")
     return out
@@ -621,17 +744,19 @@ def _req_sample(slots: Optional[torch.Tensor], positions: Optional[torch.Tensor]
 def masked_sample(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, vocab: Optional[int] = None,
                   out: Optional[torch.Tensor] = None, mask_idx: Optional[torch.Tensor] = None,
                   slots: Optional[torch.Tensor] = None, positions: Optional[torch.Tensor] = None,
-                  temperature: float = 0.0, seed: int = 0) -> torch.Tensor:
+                  temperature: float = 0.0, seed: int = 0, penalty: Optional[Penalty] = None) -> torch.Tensor:
     """:func:`masked_argmax` at a ``temperature``: ids[b] is a sample of
     softmax(logits[b] / temperature) over the allowed ids, drawn as the
     argmax of bf16 logit / T + Gumbel noise that is a hash of (``seed``,
     ``slots[b]``, ``positions[b]``, id) (:func:`dmcp.ops.reference.gumbel_noise`):
     a row's draw does not depend on its place in the batch.  Rows with
-    ``slots[b] < 0`` select 0.  Temperature 0 is :func:`masked_argmax`."""
+    ``slots[b] < 0`` select 0.  Temperature 0 is :func:`masked_argmax`.
+    ``penalty``: as :func:`masked_argmax` (the noise is added to the
+    penalised value)."""
     B = logits.shape[0] if logits.dim() == 2 else -1
     inv_t, seed = _req_sample(slots, positions, B, temperature, seed, "masked_sample")
     if inv_t == 0.0:
-        return masked_argmax(logits, mask, vocab, out, mask_idx)
+        return masked_argmax(logits, mask, vocab, out, mask_idx, penalty)
     _req(logits, torch.bfloat16, "masked_sample.logits")
     B, ld = logits.shape
     V = vocab or ld
@@ -653,6 +778,12 @@ def masked_sample(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, voc
         raise HipOpsError("masked_sample: mask_idx given without a mask table")
     out = torch.empty((B,), dtype=torch.int32, device=logits.device) if out is None else out
     _req_out(out, torch.int32, B, "masked_sample.out")
+    pen = _req_penalty(penalty, "masked_sample", B, W, n_masks or B, logits.device)
+    if pen is not None:
+        _check(lib().dmcp_masked_penal(_ptr(logits), _ptr(mask), _ptr(mask_idx if mask is not None else None),
+                                       n_masks, _ptr(out), B, V, ld, _ptr(slots), _ptr(positions), seed, inv_t,
+                                       *_pen_args(pen, W), _stream()), "dmcp_masked_penal")
+        return out
     _check(lib().dmcp_masked_sample(_ptr(logits), _ptr(mask), _ptr(mask_idx if mask is not None else None), n_masks,
                                     _ptr(out), B, V, ld, _ptr(slots), _ptr(positions), seed, inv_t, _stream()),
            "dmcp_masked_sample")
@@ -663,7 +794,8 @@ def truncated_sample(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, 
                      out: Optional[torch.Tensor] = None, mask_idx: Optional[torch.Tensor] = None,
                      slots: Optional[torch.Tensor] = None, positions: Optional[torch.Tensor] = None,
                      temperature: float = 0.0, seed: int = 0, top_k: int = 0, top_p: float = 1.0,
-                     min_p: float = 0.0, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     min_p: float = 0.0, stats: Optional[torch.Tensor] = None,
+                     penalty: Optional[Penalty] = None) -> torch.Tensor:
     """:func:`masked_sample` under top-k / top-p / min-p truncation
     (csrc/truncate.hip; the definitions: :func:`dmcp.ops.reference.truncation_threshold`):
     ids[b] is a sample of the renormalised softmax(logits[b] / temperature)
@@ -675,7 +807,9 @@ def truncated_sample(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, 
     which it equals with every filter off.  ``stats`` (int32 [B, 2]) receives
     the bf16 bits of tau (0xFF80 = -inf when no filter cuts) and the kept
     count.  Temperature 0 is :func:`masked_argmax` (``stats`` is not
-    written).  One launch, no allocation beyond ``out``; capturable."""
+    written).  One launch, no allocation beyond ``out``; capturable.
+    ``penalty``: as :func:`masked_argmax`; the thresholds, tau and the kept
+    count are those of the penalised values."""
     B = logits.shape[0] if logits.dim() == 2 else -1
     inv_t, seed = _req_sample(slots, positions, B, temperature, seed, "truncated_sample")
     try:
@@ -683,7 +817,7 @@ def truncated_sample(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, 
     except ValueError as e:
         raise HipOpsError(f"truncated_sample: {e}") from None
     if inv_t == 0.0:
-        return masked_argmax(logits, mask, vocab, out, mask_idx)
+        return masked_argmax(logits, mask, vocab, out, mask_idx, penalty)
     _req(logits, torch.bfloat16, "truncated_sample.logits")
     B, ld = logits.shape
     V = vocab or ld
@@ -707,6 +841,13 @@ def truncated_sample(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, 
         _req_out(stats, torch.int32, 2 * B, "truncated_sample.stats")
     out = torch.empty((B,), dtype=torch.int32, device=logits.device) if out is None else out
     _req_out(out, torch.int32, B, "truncated_sample.out")
+    pen = _req_penalty(penalty, "truncated_sample", B, W, n_masks or B, logits.device)
+    if pen is not None:
+        _check(lib().dmcp_truncated_penal(_ptr(logits), _ptr(mask), _ptr(mask_idx if mask is not None else None),
+                                          n_masks, _ptr(out), B, V, ld, _ptr(slots), _ptr(positions), seed, inv_t,
+                                          top_k, float(np.float32(top_p)), reference.ln_min_p(min_p), _ptr(stats),
+                                          *_pen_args(pen, W), _stream()), "dmcp_truncated_penal")
+        return out
     _check(lib().dmcp_truncated_sample(_ptr(logits), _ptr(mask), _ptr(mask_idx if mask is not None else None),
                                        n_masks, _ptr(out), B, V, ld, _ptr(slots), _ptr(positions), seed, inv_t,
                                        top_k, float(np.float32(top_p)), reference.ln_min_p(min_p), _ptr(stats),
@@ -1011,14 +1152,16 @@ def lm_head_workspace(vocab: int, device, rows: int = WGEMM_MAX_ROWS) -> torch.T
 
 
 def lm_head_argmax(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_idx: torch.Tensor,
-                   out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                   penalty: Optional[Penalty] = None) -> torch.Tensor:
     """ids[m] = argmax over the vocabulary ids allowed by mask row
     ``mask_idx[m]`` of bf16(x[m] . w[v]) -- the LM head GEMM and the grammar-
     masked greedy selection in one weight-streaming kernel + a per-row
     reduction; the [M, V] logits are never written.  x [M, K] bf16 (any M:
     chunks of WGEMM_MAX_ROWS), w [V, K] bf16, masks int32 [n_masks, ceil(V/32)],
     mask_idx int32 [M].  Ties -> lowest id; nothing allowed -> 0 (as
-    :func:`masked_argmax`).  Capturable."""
+    :func:`masked_argmax`).  Capturable.  ``penalty``: as
+    :func:`masked_argmax`, applied in the kernel's epilogue."""
     _req(x, torch.bfloat16, "lm_head_argmax.x")
     _req(w, torch.bfloat16, "lm_head_argmax.w")
     _req(masks, torch.int32, "lm_head_argmax.masks")
@@ -1038,9 +1181,16 @@ def lm_head_argmax(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_i
         workspace = lm_head_workspace(V, x.device, rows)
     if workspace.dtype != torch.float32 or workspace.numel() < 2 * (V // 64) * rows:
         raise HipOpsError("lm_head_argmax: workspace too small")
+    pen = _req_penalty(penalty, "lm_head_argmax", M, W, masks.shape[0], x.device)
     for m0 in range(0, M, WGEMM_MAX_ROWS):
         mc = min(WGEMM_MAX_ROWS, M - m0)
         mparts = -(-mc // 256)  # the fewest parts: every weight tile is read once per part
+        if pen is not None:
+            _check(lib().dmcp_lm_head_penal(_ptr(x[m0:m0 + mc]), _ptr(w), _ptr(masks), _ptr(mask_idx[m0:m0 + mc]),
+                                            masks.shape[0], W, _ptr(workspace), _ptr(out[m0:m0 + mc]), mc, V, K,
+                                            mparts, _ptr(None), _ptr(None), 0, 0.0, *_pen_args(pen, W, m0),
+                                            _stream()), "dmcp_lm_head_penal")
+            continue
         _check(lib().dmcp_lm_head_argmax(_ptr(x[m0:m0 + mc]), _ptr(w), _ptr(masks), _ptr(mask_idx[m0:m0 + mc]),
                                          masks.shape[0], W, _ptr(workspace), _ptr(out[m0:m0 + mc]), mc, V, K,
                                          mparts, _stream()), "dmcp_lm_head_argmax")
@@ -1050,7 +1200,7 @@ def lm_head_argmax(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_i
 def lm_head_sample(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_idx: torch.Tensor,
                    out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
                    slots: Optional[torch.Tensor] = None, positions: Optional[torch.Tensor] = None,
-                   temperature: float = 0.0, seed: int = 0) -> torch.Tensor:
+                   temperature: float = 0.0, seed: int = 0, penalty: Optional[Penalty] = None) -> torch.Tensor:
     """:func:`lm_head_argmax` at a ``temperature``: the same weight-streaming
     kernel, tiles, workspace and pair reduction, its epilogue perturbing each
     allowed bf16 logit / T with the Gumbel noise of :func:`masked_sample`
@@ -1060,7 +1210,7 @@ def lm_head_sample(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_i
     M = x.shape[0] if x.dim() == 2 else -1
     inv_t, seed = _req_sample(slots, positions, M, temperature, seed, "lm_head_sample")
     if inv_t == 0.0:
-        return lm_head_argmax(x, w, masks, mask_idx, out, workspace)
+        return lm_head_argmax(x, w, masks, mask_idx, out, workspace, penalty)
     _req(x, torch.bfloat16, "lm_head_sample.x")
     _req(w, torch.bfloat16, "lm_head_sample.w")
     _req(masks, torch.int32, "lm_head_sample.masks")
@@ -1080,9 +1230,16 @@ def lm_head_sample(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_i
         workspace = lm_head_workspace(V, x.device, rows)
     if workspace.dtype != torch.float32 or workspace.numel() < 2 * (V // 64) * rows:
         raise HipOpsError("lm_head_sample: workspace too small")
+    pen = _req_penalty(penalty, "lm_head_sample", M, W, masks.shape[0], x.device)
     for m0 in range(0, M, WGEMM_MAX_ROWS):
         mc = min(WGEMM_MAX_ROWS, M - m0)
         mparts = -(-mc // 256)
+        if pen is not None:
+            _check(lib().dmcp_lm_head_penal(_ptr(x[m0:m0 + mc]), _ptr(w), _ptr(masks), _ptr(mask_idx[m0:m0 + mc]),
+                                            masks.shape[0], W, _ptr(workspace), _ptr(out[m0:m0 + mc]), mc, V, K,
+                                            mparts, _ptr(slots[m0:m0 + mc]), _ptr(positions[m0:m0 + mc]), seed,
+                                            inv_t, *_pen_args(pen, W, m0), _stream()), "dmcp_lm_head_penal")
+            continue
         _check(lib().dmcp_lm_head_sample(_ptr(x[m0:m0 + mc]), _ptr(w), _ptr(masks), _ptr(mask_idx[m0:m0 + mc]),
                                          masks.shape[0], W, _ptr(workspace), _ptr(out[m0:m0 + mc]), mc, V, K,
                                          mparts, _ptr(slots[m0:m0 + mc]), _ptr(positions[m0:m0 + mc]), seed, inv_t,
@@ -1503,7 +1660,7 @@ def tgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: tor
 
 def tgemm_lm_head_argmax(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_idx: torch.Tensor,
                          out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
-                         mparts: int = 0) -> torch.Tensor:
+                         mparts: int = 0, penalty: Optional[Penalty] = None) -> torch.Tensor:
     """:func:`lm_head_argmax` on the large-tile kernel (V % 256 == 0): 256
     vocabulary ids per block, one (max, id) pair per block and row."""
     M, K, V = _tgemm_args(x, w, "tgemm_lm_head_argmax")
@@ -1521,6 +1678,12 @@ def tgemm_lm_head_argmax(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, 
     if workspace.dtype != torch.float32 or workspace.numel() < need:
         raise HipOpsError("tgemm_lm_head_argmax: workspace too small")
     mparts = mparts or tgemm_plan(M, V, K, "argmax")[1]
+    pen = _req_penalty(penalty, "tgemm_lm_head_argmax", M, W, masks.shape[0], x.device)
+    if pen is not None:
+        _check(lib().dmcp_tgemm_penal(_ptr(x), _ptr(w), _ptr(workspace), M, V, K, mparts, _ptr(masks),
+                                      _ptr(mask_idx), masks.shape[0], W, _ptr(out), _ptr(None), _ptr(None), 0, 0.0,
+                                      *_pen_args(pen, W), _stream()), "dmcp_tgemm_penal")
+        return out
     _tg(x, w, None, workspace, M, V, K, 1, mparts, 3, 0, masks, mask_idx, masks.shape[0], W, out,
         name="dmcp_tgemm[argmax]")
     return out
@@ -1530,13 +1693,13 @@ def tgemm_lm_head_sample(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, 
                          out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
                          mparts: int = 0, slots: Optional[torch.Tensor] = None,
                          positions: Optional[torch.Tensor] = None, temperature: float = 0.0,
-                         seed: int = 0) -> torch.Tensor:
+                         seed: int = 0, penalty: Optional[Penalty] = None) -> torch.Tensor:
     """:func:`lm_head_sample` on the large-tile kernel (V % 256 == 0);
     temperature 0 is :func:`tgemm_lm_head_argmax`."""
     rows = x.shape[0] if x.dim() == 2 else -1
     inv_t, seed = _req_sample(slots, positions, rows, temperature, seed, "tgemm_lm_head_sample")
     if inv_t == 0.0:
-        return tgemm_lm_head_argmax(x, w, masks, mask_idx, out, workspace, mparts)
+        return tgemm_lm_head_argmax(x, w, masks, mask_idx, out, workspace, mparts, penalty)
     M, K, V = _tgemm_args(x, w, "tgemm_lm_head_sample")
     _req(masks, torch.int32, "tgemm_lm_head_sample.masks")
     _req(mask_idx, torch.int32, "tgemm_lm_head_sample.mask_idx")
@@ -1552,6 +1715,12 @@ def tgemm_lm_head_sample(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, 
     if workspace.dtype != torch.float32 or workspace.numel() < need:
         raise HipOpsError("tgemm_lm_head_sample: workspace too small")
     mparts = mparts or tgemm_plan(M, V, K, "argmax")[1]
+    pen = _req_penalty(penalty, "tgemm_lm_head_sample", M, W, masks.shape[0], x.device)
+    if pen is not None:
+        _check(lib().dmcp_tgemm_penal(_ptr(x), _ptr(w), _ptr(workspace), M, V, K, mparts, _ptr(masks),
+                                      _ptr(mask_idx), masks.shape[0], W, _ptr(out), _ptr(slots), _ptr(positions),
+                                      seed, inv_t, *_pen_args(pen, W), _stream()), "dmcp_tgemm_penal")
+        return out
     _check(lib().dmcp_tgemm_sample(_ptr(x), _ptr(w), _ptr(workspace), M, V, K, mparts, _ptr(masks), _ptr(mask_idx),
                                    masks.shape[0], W, _ptr(out), _ptr(slots), _ptr(positions), seed, inv_t,
                                    _stream()), "dmcp_tgemm_sample")

@@ -306,11 +306,203 @@ def silu_mul(gate_up: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch
     return y
 
 
+_M32 = 0xFFFFFFFF
+
+
+# ---- repetition / presence penalty.  ``history`` is an int32 [n_slots, W]
+# bitset table (W = ceil(V / 32)), one row per KV slot: bit v of row s is set
+# once token v has been fed to slot s by a decode row (:func:`history_mark`).
+# An allowed id v of a row whose history bit v is set competes with
+#   x  = fp32(bf16 logit)
+#   y  = (x > 0 ? x * inv_theta : x * theta) - alpha      (two fp32 roundings)
+#   x' = fp32(bf16_rne(y))
+# theta the repetition penalty, inv_theta = fp32(1 / theta) computed once on
+# the host (one fp32 ulp from a division by theta), alpha the presence
+# penalty; ids whose bit is clear keep x.  x' is a bf16 value again, so every
+# selection rule works on it unchanged: greedy is the argmax of x',
+# sampling scores x' * inv_t + noise, truncation thresholds the x' values.
+# A selection under mask row r is penalised only where ``rows[r] != 0`` (None =
+# every row): the engine flags its free-text masks, not its choice masks.
+# csrc/dmcp_common.hpp penalize and the PENAL kernel variants follow these.
+def penalty_args(theta, alpha=0.0) -> tuple:
+    """(theta, fp32(1 / theta), alpha) validated: ``theta`` finite and > 0
+    with a positive finite fp32 reciprocal, ``alpha`` finite; a ValueError
+    names the offending argument."""
+    try:
+        t, a = float(theta), float(alpha)
+    except (TypeError, ValueError):
+        raise ValueError(f"theta / alpha must be numbers, got {theta!r} / {alpha!r}") from None
+    if not math.isfinite(t) or t <= 0:
+        raise ValueError(f"theta (repetition penalty) must be finite and > 0, got {theta!r}")
+    if not math.isfinite(a):
+        raise ValueError(f"alpha (presence penalty) must be finite, got {alpha!r}")
+    t = float(torch.tensor(t, dtype=torch.float32))
+    inv = float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(t, dtype=torch.float32))
+    a = float(torch.tensor(a, dtype=torch.float32))
+    if not (t > 0 and math.isfinite(inv) and inv > 0 and math.isfinite(a)):
+        raise ValueError(f"theta (repetition penalty) {theta!r} / alpha {alpha!r} are not usable fp32 numbers")
+    return t, inv, a
+
+
+def penalty_settings(repetition_penalty=1.0, presence_penalty=0.0) -> tuple:
+    """The engine's two penalty settings, validated: ``repetition_penalty``
+    finite and > 0 (1 = off), ``presence_penalty`` finite (0 = off); a
+    ValueError names the offending setting.  Returns them as floats."""
+    try:
+        theta = float(repetition_penalty)
+    except (TypeError, ValueError):
+        theta = float("nan")
+    if not math.isfinite(theta) or theta <= 0:
+        raise ValueError(f"repetition_penalty must be finite and > 0, got {repetition_penalty!r}")
+    try:
+        alpha = float(presence_penalty)
+    except (TypeError, ValueError):
+        alpha = float("nan")
+    if not math.isfinite(alpha):
+        raise ValueError(f"presence_penalty must be finite, got {presence_penalty!r}")
+    try:
+        penalty_args(theta, alpha)
+    except ValueError:
+        raise ValueError(f"repetition_penalty {repetition_penalty!r} has no usable fp32 reciprocal") from None
+    return theta, alpha
+
+
+class Penalty:
+    """The repetition / presence penalty of one selection call: ``history``
+    int32 [n_slots, W], ``slots`` int32 [rows] (each row's history row; < 0 =
+    padding, not penalised), ``theta`` / ``alpha`` as above, ``rows``
+    (optional) int32 flags per mask row.  ``off`` (theta 1, alpha 0): the
+    selection ops take their unpenalised path."""
+
+    __slots__ = ("history", "slots", "theta", "alpha", "rows", "check_slots")
+
+    def __init__(self, history, slots, theta, alpha=0.0, rows=None, check_slots=True):
+        self.history, self.slots, self.theta, self.alpha, self.rows = history, slots, theta, alpha, rows
+        # False: the caller vouches for the slot values (a device tensor is
+        # not read back: no host synchronisation; the kernels skip a slot
+        # outside the table either way)
+        self.check_slots = check_slots
+
+    @property
+    def off(self) -> bool:
+        return self.theta == 1 and self.alpha == 0
+
+    def check(self, name: str, B: int, W: int, n_rows: int, values: bool = True, device=None) -> tuple:
+        """Validate against a launch of ``B`` rows, ``W`` mask words per row
+        and ``n_rows`` mask rows; returns (theta, inv_theta, alpha) as fp32
+        values.  ``values``: also read ``slots`` to check every live slot
+        against the table (a device tensor is read back)."""
+        try:
+            keys = penalty_args(self.theta, self.alpha)
+        except ValueError as e:
+            raise ValueError(f"{name}: penalty {e}") from None
+        h, sl, rw = self.history, self.slots, self.rows
+        if isinstance(h, torch.Tensor) and device is not None and h.device != device:
+            raise ValueError(f"{name}: penalty history is on {h.device}, the selection's input on {device}")
+        if (not isinstance(h, torch.Tensor) or h.dtype != torch.int32 or h.dim() != 2 or not h.is_contiguous()
+                or h.shape[0] < 1 or h.shape[1] != W):
+            raise ValueError(f"{name}: penalty history must be a contiguous int32 [n_slots, {W}] bitset table")
+        if (not isinstance(sl, torch.Tensor) or sl.dtype != torch.int32 or sl.numel() != B
+                or not sl.is_contiguous() or sl.device != h.device):
+            raise ValueError(f"{name}: penalty slots must be int32 [{B}] on the history's device")
+        if values and self.check_slots and B > 0 and int(sl.max()) >= h.shape[0]:
+            raise ValueError(f"{name}: penalty slots reach {int(sl.max())}, the history has {h.shape[0]} rows")
+        if rw is not None and (not isinstance(rw, torch.Tensor) or rw.dtype != torch.int32 or rw.numel() != n_rows
+                               or not rw.is_contiguous() or rw.device != h.device):
+            raise ValueError(f"{name}: penalty rows must be int32 [{n_rows}] (one flag per mask row)")
+        return keys
+
+
+def unpack_bits(words: torch.Tensor, vocab: int) -> torch.Tensor:
+    """bool [..., vocab] of int32 bitset rows [..., >= ceil(vocab / 32)]."""
+    idx = torch.arange(vocab, device=words.device)
+    return ((words.to(torch.int64)[..., idx // 32] >> (idx % 32)) & 1) != 0
+
+
+def penalize(logits: torch.Tensor, history_rows: Optional[torch.Tensor], theta: float, alpha: float = 0.0
+             ) -> torch.Tensor:
+    """fp32 [B, V] of the penalised values x' defined above: ``logits`` [B, V]
+    (rounded to bf16 first), ``history_rows`` int32 [B, >= ceil(V / 32)] bitset
+    rows (None = nothing seen).  Every selection reference calls this."""
+    x = logits.to(torch.bfloat16).float()
+    if history_rows is None:
+        return x
+    t, inv, a = (torch.tensor(v, dtype=torch.float32, device=x.device) for v in penalty_args(theta, alpha))
+    y = (torch.where(x > 0, x * inv, x * t) - a).to(torch.bfloat16).float()
+    return torch.where(unpack_bits(history_rows, x.shape[-1]), y, x)
+
+
+def _mask_rows(B: int, mask, mask_idx, device) -> torch.Tensor:
+    """The mask row index of each logits row (row b itself without ``mask_idx``)."""
+    if mask is not None and mask_idx is not None:
+        return mask_idx.long().clamp(0, mask.shape[0] - 1)
+    return torch.arange(B, device=device)
+
+
+def penalized(logits: torch.Tensor, vocab: int, mask, mask_idx, penalty: Optional[Penalty], name: str) -> torch.Tensor:
+    """fp32 [B, V] values a selection compares: the bf16 logits, penalised
+    where ``penalty`` (None or off: nowhere) covers the row -- its slot is
+    inside the table and its mask row's flag is set."""
+    B = logits.shape[0]
+    x = logits[:, :vocab].to(torch.bfloat16).float()
+    if penalty is None or penalty.off:
+        return x
+    n_rows = mask.shape[0] if (mask is not None and mask_idx is not None) else B
+    theta, _, alpha = penalty.check(name, B, (vocab + 31) // 32, n_rows, device=logits.device)
+    sl = penalty.slots.long()
+    on = sl >= 0
+    if penalty.rows is not None:
+        on = on & (penalty.rows[_mask_rows(B, mask, mask_idx, logits.device)] != 0)
+    rows = penalty.history[sl.clamp(0, penalty.history.shape[0] - 1)]
+    rows = torch.where(on[:, None], rows, torch.zeros_like(rows))
+    return penalize(x, rows, theta, alpha)
+
+
+def history_mark(history: torch.Tensor, tokens: torch.Tensor, slots: torch.Tensor,
+                 src: Optional[torch.Tensor] = None, last_ids: Optional[torch.Tensor] = None,
+                 exempt: Optional[torch.Tensor] = None, vocab: Optional[int] = None) -> torch.Tensor:
+    """Record the tokens a decode step feeds: for every row r with
+    ``slots[r]`` inside the table, set bit t of ``history[slots[r]]``, t =
+    ``last_ids[src[r]]`` where ``src[r] >= 0`` else ``tokens[r]`` (the gather
+    of :func:`decode_embed_norm`); tokens outside [0, vocab) and ids whose bit
+    is set in ``exempt`` (int32 [W]) are not recorded.  In place."""
+    W = history.shape[1]
+    V = vocab or 32 * W
+    toks = tokens.long()
+    if src is not None:
+        s = src.long()
+        toks = torch.where(s >= 0, last_ids.long()[s.clamp(0, last_ids.numel() - 1)], toks)
+    sl = slots.long()
+    ok = (sl >= 0) & (sl < history.shape[0]) & (toks >= 0) & (toks < V)
+    if exempt is not None:
+        ex = (exempt.to(torch.int64)[(toks.clamp(0, V - 1)) // 32] >> (toks.clamp(0, V - 1) % 32)) & 1
+        ok = ok & (ex == 0)
+    h64 = history.to(torch.int64) & _M32
+    for r in torch.nonzero(ok).flatten().tolist():
+        t = int(toks[r])
+        h64[int(sl[r]), t // 32] |= 1 << (t % 32)
+    history.copy_(torch.where(h64 >= 2 ** 31, h64 - 2 ** 32, h64).to(torch.int32))
+    return history
+
+
+def history_reset(history: torch.Tensor, slots) -> torch.Tensor:
+    """Zero the history rows of ``slots`` (a sequence of ints; entries outside
+    the table are ignored).  In place."""
+    for s in slots:
+        if 0 <= int(s) < history.shape[0]:
+            history[int(s)].zero_()
+    return history
+
+
 def masked_argmax(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, vocab: Optional[int] = None,
-                  out: Optional[torch.Tensor] = None, mask_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None, mask_idx: Optional[torch.Tensor] = None,
+                  penalty: Optional[Penalty] = None) -> torch.Tensor:
     B, ld = logits.shape
     V = vocab or ld
-    x = logits[:, :V].float().clone()
+    if penalty is None or penalty.off:
+        x = logits[:, :V].float().clone()
+    else:
+        x = penalized(logits, V, mask, mask_idx, penalty, "masked_argmax")
     if mask is not None and mask_idx is not None:
         mask = mask[mask_idx.long().clamp(0, mask.shape[0] - 1)]
     if mask is not None:
@@ -326,10 +518,11 @@ def masked_argmax(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, voc
 
 
 def lm_head_argmax(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_idx: torch.Tensor,
-                   out: Optional[torch.Tensor] = None, workspace=None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, workspace=None,
+                   penalty: Optional[Penalty] = None) -> torch.Tensor:
     """The fused LM head + masked argmax's definition: F.linear then masked_argmax."""
     logits = (x.float() @ w.float().t()).to(torch.bfloat16)
-    return masked_argmax(logits, masks, w.shape[0], out, mask_idx)
+    return masked_argmax(logits, masks, w.shape[0], out, mask_idx, penalty)
 
 
 # ---- temperature sampling as a perturbed argmax (Gumbel-max).  The noise is
@@ -342,7 +535,6 @@ def lm_head_argmax(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_i
 #   u = ((bits >> 9) + 0.5) * 2^-23       (exact in fp32, never 0 or 1)
 #   g = -log(-log(u))
 #   score(row, v) = bf16(logit) * fp32(1 / T) + g
-_M32 = 0xFFFFFFFF
 _GOLD = 0x9E3779B1
 
 
@@ -385,18 +577,21 @@ def _sample_args(B: int, slots, positions, temperature) -> float:
 
 def sample_scores(logits: torch.Tensor, mask: Optional[torch.Tensor], vocab: Optional[int],
                   mask_idx: Optional[torch.Tensor], slots: torch.Tensor, positions: torch.Tensor,
-                  temperature: float, seed: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+                  temperature: float, seed: int, dtype: torch.dtype = torch.float32,
+                  penalty: Optional[Penalty] = None) -> torch.Tensor:
     """The scores [B, V] whose row-wise argmax :func:`masked_sample` returns
     (temperature > 0): bf16(logit) * fp32(1 / T) + Gumbel noise in ``dtype``
     (fp32 as the kernels compute, fp64 for tests), -inf for the ids the row's
-    mask excludes and for every id of a row whose slot is < 0."""
+    mask excludes and for every id of a row whose slot is < 0.  Under a
+    ``penalty`` the bf16 logit is the penalised value (:func:`penalize`)."""
     B, ld = logits.shape
     t = _sample_args(B, slots, positions, temperature)
     if t == 0:
         raise ValueError("sample_scores: temperature must be > 0")
     V = vocab or ld
     inv_t = float(torch.tensor(1.0 / t, dtype=torch.float32))
-    x = logits[:, :V].to(torch.bfloat16).to(dtype) * inv_t + gumbel_noise(seed, slots, positions, V, dtype)
+    x = (penalized(logits, V, mask, mask_idx, penalty, "masked_sample").to(dtype) * inv_t
+         + gumbel_noise(seed, slots, positions, V, dtype))
     if mask is not None and mask_idx is not None:
         mask = mask[mask_idx.long().clamp(0, mask.shape[0] - 1)]
     if mask is not None:
@@ -411,14 +606,14 @@ def sample_scores(logits: torch.Tensor, mask: Optional[torch.Tensor], vocab: Opt
 def masked_sample(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, vocab: Optional[int] = None,
                   out: Optional[torch.Tensor] = None, mask_idx: Optional[torch.Tensor] = None,
                   slots: Optional[torch.Tensor] = None, positions: Optional[torch.Tensor] = None,
-                  temperature: float = 0.0, seed: int = 0) -> torch.Tensor:
+                  temperature: float = 0.0, seed: int = 0, penalty: Optional[Penalty] = None) -> torch.Tensor:
     """:func:`masked_argmax` at a temperature: the allowed id with the highest
     bf16(logit) / T + Gumbel noise, an exact sample of softmax(logits / T) over
     the allowed ids; the lowest id among ties, 0 when nothing is allowed or the
     row's slot is < 0 (padding).  Temperature 0 is :func:`masked_argmax`."""
     if _sample_args(logits.shape[0], slots, positions, temperature) == 0:
-        return masked_argmax(logits, mask, vocab, out, mask_idx)
-    x = sample_scores(logits, mask, vocab, mask_idx, slots, positions, temperature, seed)
+        return masked_argmax(logits, mask, vocab, out, mask_idx, penalty)
+    x = sample_scores(logits, mask, vocab, mask_idx, slots, positions, temperature, seed, penalty=penalty)
     ids = torch.argmax(x, dim=-1).to(torch.int32)  # first index among ties; 0 for an all -inf row
     if out is not None:
         out.copy_(ids)
@@ -429,10 +624,10 @@ def masked_sample(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, voc
 def lm_head_sample(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_idx: torch.Tensor,
                    out: Optional[torch.Tensor] = None, workspace=None, slots: Optional[torch.Tensor] = None,
                    positions: Optional[torch.Tensor] = None, temperature: float = 0.0,
-                   seed: int = 0) -> torch.Tensor:
+                   seed: int = 0, penalty: Optional[Penalty] = None) -> torch.Tensor:
     """The fused LM head + sampling's definition: F.linear then masked_sample."""
     logits = (x.float() @ w.float().t()).to(torch.bfloat16)
-    return masked_sample(logits, masks, w.shape[0], out, mask_idx, slots, positions, temperature, seed)
+    return masked_sample(logits, masks, w.shape[0], out, mask_idx, slots, positions, temperature, seed, penalty)
 
 
 # ---- top-k / top-p / min-p truncation of the sampled selection.  Per row: A =
@@ -495,7 +690,7 @@ def _allowed(logits: torch.Tensor, mask, vocab, mask_idx, slots) -> torch.Tensor
 def truncation_threshold(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, vocab: Optional[int] = None,
                          mask_idx: Optional[torch.Tensor] = None, slots: Optional[torch.Tensor] = None,
                          temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
-                         min_p: float = 0.0) -> tuple:
+                         min_p: float = 0.0, penalty: Optional[Penalty] = None) -> tuple:
     """(tau fp32 [B], kept count int64 [B], ambiguous bool [B]) of the
     definitions above, thresholds in fp64 (the min-p comparison in fp32, as
     defined).  tau is -inf where no filter is on, the mask allows nothing or
@@ -511,7 +706,8 @@ def truncation_threshold(logits: torch.Tensor, mask: Optional[torch.Tensor] = No
     if slots is None:
         slots = torch.zeros(B, dtype=torch.int32, device=logits.device)
     inv_t = float(torch.tensor(1.0 / t, dtype=torch.float32))
-    x = logits[:, :V].to(torch.bfloat16).float() + 0.0  # -0 -> +0: a threshold on the value
+    # -0 -> +0: a threshold on the value (the penalised value under a penalty)
+    x = penalized(logits, V, mask, mask_idx, penalty, "truncation_threshold") + 0.0
     ok = _allowed(logits, mask, V, mask_idx, slots)
     tau = torch.full((B,), float("-inf"), dtype=torch.float32)
     kept = torch.zeros(B, dtype=torch.int64)
@@ -550,15 +746,16 @@ def tau_bits(tau: torch.Tensor) -> torch.Tensor:
 def truncated_sample_at(tau: torch.Tensor, logits: torch.Tensor, mask: Optional[torch.Tensor] = None,
                         vocab: Optional[int] = None, mask_idx: Optional[torch.Tensor] = None,
                         slots: Optional[torch.Tensor] = None, positions: Optional[torch.Tensor] = None,
-                        temperature: float = 1.0, seed: int = 0) -> tuple:
+                        temperature: float = 1.0, seed: int = 0, penalty: Optional[Penalty] = None) -> tuple:
     """(ids int32 [B], kept count [B]) of the sampled selection over the
     allowed ids whose value is >= ``tau`` (fp32 [B]): what
     :func:`truncated_sample` returns for its own thresholds, and the expected
     result at a neighbouring value level for a row whose top-p sum is
     ambiguous."""
     V = vocab or logits.shape[1]
-    scores = sample_scores(logits, mask, vocab, mask_idx, slots, positions, temperature, seed)
-    cut = logits[:, :V].to(torch.bfloat16).float() < tau.to(torch.float32).to(logits.device)[:, None]
+    scores = sample_scores(logits, mask, vocab, mask_idx, slots, positions, temperature, seed, penalty=penalty)
+    cut = (penalized(logits, V, mask, mask_idx, penalty, "truncated_sample")
+           < tau.to(torch.float32).to(logits.device)[:, None])
     kept = (_allowed(logits, mask, V, mask_idx, slots) & ~cut).sum(dim=1)
     scores[cut] = float("-inf")
     return torch.argmax(scores, dim=-1).to(torch.int32), kept  # first index among ties; 0 for an all -inf row
@@ -568,7 +765,8 @@ def truncated_sample(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, 
                      out: Optional[torch.Tensor] = None, mask_idx: Optional[torch.Tensor] = None,
                      slots: Optional[torch.Tensor] = None, positions: Optional[torch.Tensor] = None,
                      temperature: float = 0.0, seed: int = 0, top_k: int = 0, top_p: float = 1.0,
-                     min_p: float = 0.0, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     min_p: float = 0.0, stats: Optional[torch.Tensor] = None,
+                     penalty: Optional[Penalty] = None) -> torch.Tensor:
     """:func:`masked_sample` over the ids :func:`truncation_threshold` keeps:
     the kept id with the highest score of :func:`sample_scores`, the lowest id
     among ties, 0 when nothing is allowed or the row's slot is < 0.
@@ -577,9 +775,10 @@ def truncated_sample(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, 
     the bf16 bits of tau and the kept count."""
     top_k, top_p, min_p = truncation_args(top_k, top_p, min_p)
     if _sample_args(logits.shape[0], slots, positions, temperature) == 0:
-        return masked_argmax(logits, mask, vocab, out, mask_idx)
-    tau, kept, _ = truncation_threshold(logits, mask, vocab, mask_idx, slots, temperature, top_k, top_p, min_p)
-    ids, _ = truncated_sample_at(tau, logits, mask, vocab, mask_idx, slots, positions, temperature, seed)
+        return masked_argmax(logits, mask, vocab, out, mask_idx, penalty)
+    tau, kept, _ = truncation_threshold(logits, mask, vocab, mask_idx, slots, temperature, top_k, top_p, min_p,
+                                        penalty)
+    ids, _ = truncated_sample_at(tau, logits, mask, vocab, mask_idx, slots, positions, temperature, seed, penalty)
     if stats is not None:
         stats.copy_(torch.stack([tau_bits(tau), kept.to(torch.int32)], dim=1).to(stats.device))
     if out is not None:

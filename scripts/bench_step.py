@@ -58,6 +58,8 @@ def main(argv=None) -> int:
     ap.add_argument("--top-k", type=int, default=0, help="top-k truncation of the sampled step (0 = off)")
     ap.add_argument("--top-p", type=float, default=1.0, help="top-p truncation (1 = off)")
     ap.add_argument("--min-p", type=float, default=0.0, help="min-p truncation (0 = off)")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0, help="repetition penalty (1 = off)")
+    ap.add_argument("--presence-penalty", type=float, default=0.0, help="presence penalty (0 = off)")
     a = ap.parse_args(argv)
 
     from dmcp.enrich.local import LocalEngine
@@ -82,7 +84,8 @@ def main(argv=None) -> int:
         model.tg_head = False
     hip.wgemm_set_aux(a.wgemm_aux)
     cut = {"top_k": a.top_k, "top_p": a.top_p, "min_p": a.min_p} if (a.top_k, a.top_p, a.min_p) != (0, 1.0, 0.0) else {}
-    eng = LocalEngine(model, **({"temperature": a.temperature, "seed": a.seed, **cut} if a.temperature > 0 else {}))
+    eng = LocalEngine(model, repetition_penalty=a.repetition_penalty, presence_penalty=a.presence_penalty,
+                      **({"temperature": a.temperature, "seed": a.seed, **cut} if a.temperature > 0 else {}))
     g = torch.Generator().manual_seed(0)
     if a.prefix:
         model.set_prefix(torch.randint(0, 256, (a.prefix,), generator=g).tolist())
@@ -132,7 +135,8 @@ def main(argv=None) -> int:
     loop_ms = (time.perf_counter() - t0) / a.iters * 1e3
     kv_bytes = 2 * cfg.layers * cfg.n_kv_heads * cfg.head_dim * cfg.kv_elem_bytes * (sum(ctxs) + a.batch + a.prefix)
     w_bytes = 2 * (cfg.param_count() - cfg.vocab_size * cfg.hidden)
-    print(json.dumps({"bench": "decode_step", "preset": a.preset, "kv_dtype": a.kv_dtype, "decode_dtype": a.decode_dtype, "temperature": a.temperature, "top_k": a.top_k, "top_p": a.top_p, "min_p": a.min_p, "rows": n,
+    print(json.dumps({"bench": "decode_step", "preset": a.preset, "kv_dtype": a.kv_dtype, "decode_dtype": a.decode_dtype, "temperature": a.temperature, "top_k": a.top_k, "top_p": a.top_p, "min_p": a.min_p,
+                      "repetition_penalty": a.repetition_penalty, "presence_penalty": a.presence_penalty, "rows": n,
                       "graph_kernels": graphs.graphs[graphs.bucket_for(n)].kernels, "batch": a.batch, "prefix": a.prefix,
                       "ctx": a.ctx, "jitter": a.jitter, "adjacent": a.adjacent, "fused": bool(getattr(model, "use_fused", False)),
                       "tgemm": bool(getattr(model, "use_tgemm", False)),
