@@ -96,6 +96,11 @@ class Config:
     # dmcp/ops/reference.py penalize.  Checked when the engine is built.
     local_llm_repetition_penalty: float = 1.0
     local_llm_presence_penalty: float = 0.0
+    # the chat turn the prompt is wrapped in: "auto" = the checkpoint's own
+    # chat template when it has one (raw text otherwise: the presets have
+    # none), "off" = raw text, else a path to a Jinja file used instead of
+    # the checkpoint's -- dmcp/enrich/chat.py.  Checked when the engine is built.
+    local_llm_chat_template: str = "auto"
     local_llm_devices: str = "all"
     # "process": one worker process per GPU, started before this process
     # touches HIP (the service default); "inline": engines in this process
@@ -180,6 +185,7 @@ class Config:
             "LOCAL_LLM_MIN_P": "local_llm_min_p",
             "LOCAL_LLM_REPETITION_PENALTY": "local_llm_repetition_penalty",
             "LOCAL_LLM_PRESENCE_PENALTY": "local_llm_presence_penalty",
+            "LOCAL_LLM_CHAT_TEMPLATE": "local_llm_chat_template",
             "LOCAL_LLM_DEVICES": "local_llm_devices",
             "LOCAL_LLM_WORKERS": "local_llm_workers",
             "LOCAL_LLM_MAX_BATCH": "local_llm_max_batch",

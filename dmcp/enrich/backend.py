@@ -466,7 +466,7 @@ def create_backend(cfg) -> EnrichmentBackend:
             # headers only: no worker process, no tensor data) is refused here,
             # not loaded as some other model
             from ..models.llm import check_checkpoint
-            why = check_checkpoint(path)
+            why = check_checkpoint(path, chat_template=getattr(cfg, "local_llm_chat_template", "auto"))
             if why is not None:
                 reason = (f"ENRICH_BACKEND=local cannot load the checkpoint LOCAL_LLM_MODEL_PATH={path}: {why}. "
                           f"Supported: Llama, Qwen2 and Qwen3 checkpoints (docs/PARITY.md)")

@@ -55,6 +55,7 @@ import torch
 from ..models.llm import LocalLM, LMConfig, DecodeGraphs, preset
 from ..ops.reference import penalty_settings, truncation_args
 from .backend import SYNTHETIC_PREFIX, EnrichmentBackend, build_enrichment_prompt
+from .chat import resolve as resolve_chat
 from .jsonfix import parse_enrichment_response
 from .tokenizer import ByteTokenizer
 from .tokenizer import _Base as _TokBase
@@ -501,6 +502,15 @@ class LocalEngine:
 
     ``tokenizer``: the vocabulary of ``model`` (:mod:`dmcp.enrich.tokenizer`);
     default the byte-level one of the built-in presets.
+
+    ``chat_template`` (``LOCAL_LLM_CHAT_TEMPLATE``): ``auto`` wraps every
+    prompt in the one user turn of the checkpoint's chat template when the
+    tokenizer's directory has one (:mod:`dmcp.enrich.chat`); ``off`` never;
+    else a Jinja file used instead.  The prompt is then ``head_ids + content
+    + tail_ids`` (:meth:`_chat_prompt`), the shared prefix begins with the
+    turn header, and the reply starts right after ``tail_ids``; grammar,
+    forks and jump-forward are the same.  :attr:`chat_mode` says which mode
+    was resolved (``raw`` or ``template:<file>``).
     """
 
     MASK_NO_QUOTE, MASK_QUOTE = 0, 1
@@ -516,7 +526,8 @@ class LocalEngine:
                  reply_shape: Optional[ReplyShape] = None, type_choice: Optional[bool] = None,
                  precapture: Optional[bool] = None, temperature: float = 0.0, seed: int = 0,
                  top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0,
-                 repetition_penalty: float = 1.0, presence_penalty: float = 0.0) -> None:
+                 repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                 chat_template: str = "auto") -> None:
         self.model = model
         self.repetition_penalty, self.presence_penalty = penalty_settings(repetition_penalty, presence_penalty)
         # temperature 0 (the default) is the greedy selection, unchanged; above
@@ -550,6 +561,23 @@ class LocalEngine:
         self._quote = self.tok.quote
         if len(self._tb) < model.cfg.vocab_size:  # ids the tokenizer does not name append nothing
             self._tb = list(self._tb) + [b""] * (model.cfg.vocab_size - len(self._tb))
+        # the chat turn around every prompt (dmcp/enrich/chat.py): the
+        # checkpoint's own template ("auto"; the presets and a directory
+        # without one have none: raw text behind a BOS, as ever), "off", or a
+        # Jinja file.  Rendered once, here: head_ids / tail_ids are constant
+        # for the engine's life, so the prefix cache stays valid.  The
+        # template's own BOS text is the only BOS (tok.bos is not prepended).
+        self.chat_mode, self.chat = resolve_chat(self.tok, chat_template)
+        self.head_ids: List[int] = []
+        self.tail_ids: List[int] = []
+        if self.chat is not None:
+            self.head_ids = self.tok.encode(self.chat.head_text)
+            self.tail_ids = self.tok.encode(self.chat.tail_text)
+            bad = [i for i in self.head_ids + self.tail_ids if not 0 <= i < model.cfg.vocab_size]
+            if bad:  # a turn marker past the embedding table would be read out of bounds
+                raise ValueError(f"chat template of {self.chat.source}: token id {bad[0]} of the rendered turn "
+                                 f"is outside the model's vocabulary of {model.cfg.vocab_size}")
+        LOG.info("local engine: chat template %s", self.chat_mode)
         # admit the pending classes with the longest reply budget first (LPT):
         # the run's tail is then short replies, not a few long ones decoding
         # alone in a nearly empty batch
@@ -860,6 +888,8 @@ class LocalEngine:
     # ------------------------------------------------------------ helpers
     def _prompt(self, seq: _Seq, readme: Optional[str], budget: int) -> List[int]:
         """Prompt tokens of ``seq``; sets ``seq.prefix_split``."""
+        if self.chat is not None:
+            return self._chat_prompt(seq, readme, budget)
         text = build_enrichment_prompt(seq.inp, readme)
         i = text.find(PREFIX_MARKER.decode())
         if i > 0:  # the per-project text (instructions + README) is tokenised once per project
@@ -888,6 +918,44 @@ class LocalEngine:
         seq.prefix_split = split
         return ids
 
+    def _chat_prompt(self, seq: _Seq, readme: Optional[str], budget: int) -> List[int]:
+        """:meth:`_prompt` inside the chat turn: ``head_ids + content +
+        tail_ids``.  The content is the stripped prompt text (a template's
+        ``| trim`` is then a no-op), tokenised with no special token
+        recognised in it (untrusted source) and in the same two parts as
+        the raw prompt, so the shared prefix -- now beginning with the turn
+        header -- is still the same ids for every class of a project.
+        Truncation cuts content only; ``max_prompt_tokens`` bounds everything
+        after the head (as it bounds everything after the BOS of a raw prompt)."""
+        text = build_enrichment_prompt(seq.inp, readme).strip()
+        head, tail = self.head_ids, self.tail_ids
+        i = text.find(PREFIX_MARKER.decode())
+        if i > 0:
+            pre = self._prefix_cache.get(text[:i])
+            if pre is None:
+                if len(self._prefix_cache) >= 8:
+                    self._prefix_cache.clear()
+                pre = self._prefix_cache[text[:i]] = head + self.tok.encode_plain(text[:i])
+            cont = self._cont_cache.get(text[i:])
+            ids, split = pre + (cont if cont is not None else self.tok.encode_plain_continuation(text[i:])), len(pre)
+        else:
+            ids, split = head + self.tok.encode_plain(text), 0
+        # head + limit tokens at the most, limit as for a raw prompt (whose head is the BOS)
+        limit = self.cfg.max_seq - budget - 1 - len(head)
+        if self.max_prompt_tokens:
+            limit = min(limit, self.max_prompt_tokens)
+        limit -= len(tail)  # content tokens
+        if limit < 16:
+            raise ValueError("KV capacity too small for the chat turn and the reply template")
+        if len(ids) - len(head) > limit:
+            keep_tail = min(256, limit // 4)  # keep the instructions at the end
+            cut = len(head) + limit - keep_tail
+            ids = ids[:cut] + ids[len(ids) - keep_tail:]
+            if split > cut:  # the marker was cut out: no shared prefix
+                split = 0
+        seq.prefix_split = split
+        return ids + tail
+
     def _pretokenize(self, items, readme: Optional[str]) -> None:
         """The per-class parts of the prompts of ``items`` (feed items: key,
         input[, readme]) in one batched tokenizer call, for :meth:`_prompt`.
@@ -901,11 +969,15 @@ class LocalEngine:
         todo = []
         for item in items:
             text = build_enrichment_prompt(item[1], item[2] if len(item) > 2 else readme)
+            if self.chat is not None:
+                text = text.strip()  # as _chat_prompt looks it up
             i = text.find(marker)
             if i > 0 and text[i:] not in self._cont_cache:
                 todo.append(text[i:])
         if len(todo) > 1:
-            self._cont_cache.update(zip(todo, self.tok.encode_continuation_batch(todo)))
+            batch = self.tok.encode_plain_continuation_batch if self.chat is not None else \
+                self.tok.encode_continuation_batch
+            self._cont_cache.update(zip(todo, batch(todo)))
 
     def _seq_prefix_len(self, s: _Seq) -> int:
         """Tokens of ``s.prompt`` before its per-class part, or 0."""
@@ -1737,7 +1809,8 @@ def build_model(spec: dict, device: str):
     overrides = {k: spec[k] for k in ("kv_dtype", "prefill_dtype", "decode_dtype", "max_batch", "max_rows", "max_seq") if k in spec}
     if spec.get("path"):
         from .tokenizer import load_local_model
-        return load_local_model(spec["path"], device=device, **overrides)
+        return load_local_model(spec["path"], device=device, chat_template=spec.get("chat_template", "auto"),
+                                **overrides)
     cfg = preset(spec.get("preset", "dmcp-coder-1b"), **overrides)
     model = LocalLM(cfg, device=device, seed=int(spec.get("seed", 0)))
     if cfg.tokenizer:

@@ -48,12 +48,13 @@ class _Base:
     def encode(self, text: str) -> List[int]:
         raise NotImplementedError
 
-    def encode_fragment(self, text: str) -> List[int]:
+    def encode_fragment(self, text: str, encode=None) -> List[int]:
         """Ids that decode to exactly ``text`` wherever they are spliced in
         (forced reply skeleton).  A tokenizer whose pre-tokenizer rewrites the
         start of a text (SentencePiece's dummy-prefix space) falls back to one
-        single-byte token per byte."""
-        ids = self.encode(text)
+        single-byte token per byte.  ``encode``: the encoder to use instead
+        of :meth:`encode`."""
+        ids = (encode or self.encode)(text)
         raw = text.encode("utf-8")
         tb = self.token_bytes
         if b"".join(map(tb.__getitem__, ids)) == raw:
@@ -113,7 +114,7 @@ class _Base:
         tokenizer encodes them in parallel)."""
         return [self.encode_continuation(t) for t in texts]
 
-    def _continuation(self, text: str, ids: List[int]) -> List[int]:
+    def _continuation(self, text: str, ids: List[int], encode=None) -> List[int]:
         raw = text.encode("utf-8")
         tb = self.token_bytes
         got = b"".join(map(tb.__getitem__, ids))
@@ -125,8 +126,8 @@ class _Base:
             # "▁Source" as one piece: re-spell the first piece's text without the space
             first = tb[ids[0]]
             if first.startswith(b" ") and b"".join(tb[i] for i in ids[1:]) == raw[len(first) - 1:]:
-                return self.encode_fragment(first[1:].decode("utf-8", "replace")) + ids[1:]
-        return self.encode_fragment(text)
+                return self.encode_fragment(first[1:].decode("utf-8", "replace"), encode) + ids[1:]
+        return self.encode_fragment(text, encode)
 
 
 class ByteTokenizer(_Base):
@@ -207,6 +208,10 @@ class HFTokenizer(_Base):
         if self.quote < 0:
             raise ValueError(f"tokenizer {file}: no token spells '\"' alone")
         self.bos = bos
+        self.special_ids = frozenset(special)
+        self.checkpoint_dir: Optional[str] = None  # set by load_tokenizer: where a chat template is looked for
+        self._text = text
+        self._plain = None
 
     def encode(self, text: str) -> List[int]:
         return self.tk.encode(text, add_special_tokens=False).ids
@@ -216,6 +221,33 @@ class HFTokenizer(_Base):
         # GIL released: 64 prompts of ~500 tokens in ~11 ms instead of ~60 ms
         encs = self.tk.encode_batch(list(texts), add_special_tokens=False)
         return [self._continuation(t, e.ids) for t, e in zip(texts, encs)]
+
+    # Untrusted text (the content of a chat turn: instructions, README, class
+    # source).  ``encode`` recognises the special tokens' texts wherever they
+    # occur -- right for a rendered template's own markers; in content a Java
+    # string literal holding "<|im_end|>" would close the turn.  A second
+    # instance of the same tokenizer with ``encode_special_tokens`` on spells
+    # them as ordinary pieces.
+    def _plain_tk(self):
+        if self._plain is None:
+            from tokenizers import Tokenizer
+            tk = Tokenizer.from_str(self._text)
+            tk.encode_special_tokens = True
+            self._plain = tk
+        return self._plain
+
+    def encode_plain(self, text: str) -> List[int]:
+        """Ids of ``text`` with no special token recognised in it."""
+        return self._plain_tk().encode(text, add_special_tokens=False).ids
+
+    def encode_plain_continuation(self, text: str) -> List[int]:
+        """:meth:`encode_continuation` with no special token recognised."""
+        return self._continuation(text, self.encode_plain(text), self.encode_plain)
+
+    def encode_plain_continuation_batch(self, texts: Sequence[str]) -> List[List[int]]:
+        """:meth:`encode_continuation_batch` with no special token recognised."""
+        encs = self._plain_tk().encode_batch(list(texts), add_special_tokens=False)
+        return [self._continuation(t, e.ids, self.encode_plain) for t, e in zip(texts, encs)]
 
 
 def load_tokenizer(path: str) -> HFTokenizer:
@@ -231,7 +263,10 @@ def load_tokenizer(path: str) -> HFTokenizer:
             with open(tc) as f:
                 if json.load(f).get("add_bos_token") is False:
                     bos = None
-    return HFTokenizer(path, bos=bos if isinstance(bos, int) else None)
+    tok = HFTokenizer(path, bos=bos if isinstance(bos, int) else None)
+    if os.path.isdir(path):
+        tok.checkpoint_dir = path
+    return tok
 
 
 ASSETS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "models", "assets")
@@ -255,10 +290,17 @@ def load_asset_tokenizer(name: str) -> HFTokenizer:
     return tok
 
 
-def load_local_model(path: str, device: str = "cuda", **cfg_overrides):
+def load_local_model(path: str, device: str = "cuda", chat_template: str = "auto", **cfg_overrides):
     """(LocalLM, tokenizer) of a Llama-format checkpoint directory
-    (``config.json`` + ``*.safetensors`` + ``tokenizer.json``)."""
-    from ..models.llm import LocalLM
+    (``config.json`` + ``*.safetensors`` + ``tokenizer.json``).
+    ``chat_template``: the ``LOCAL_LLM_CHAT_TEMPLATE`` knob the engine will
+    get -- a chat template it selects that cannot be used is refused here
+    (:class:`CheckpointUnsupported`), before any tensor is read."""
+    from ..models.llm import CheckpointUnsupported, LocalLM
+    from .chat import template_problem
+    reason = template_problem(path, chat_template)
+    if reason is not None:
+        raise CheckpointUnsupported(f"{path}: {reason}")
     model = LocalLM.load_safetensors(path, device=device, **cfg_overrides)
     tok = load_tokenizer(path)
     if len(tok.token_bytes) > model.cfg.vocab_size:

@@ -323,7 +323,8 @@ class GpuWorkerPool:
                     who.ready = True
                     who.info = msg
                     self._rebalance()
-                LOG.info("GPU worker %d ready on %s (pid %s)", who.index, who.device, msg.get("pid"))
+                LOG.info("GPU worker %d ready on %s (pid %s, chat template %s)", who.index, who.device,
+                         msg.get("pid"), (msg.get("witness") or {}).get("chat_template", "n/a"))
         if not any(w.ready and w.alive for w in self.workers):
             raise RuntimeError("no GPU worker started")
         self._initialised = True
@@ -658,6 +659,8 @@ def model_spec(cfg) -> dict:
             "decode_dtype": getattr(cfg, "local_llm_decode_dtype", "bf16")}
     if getattr(cfg, "local_llm_model_path", ""):
         spec["path"] = cfg.local_llm_model_path
+        # the loader refuses a checkpoint whose selected chat template cannot be used
+        spec["chat_template"] = str(getattr(cfg, "local_llm_chat_template", "auto") or "auto")
     return spec
 
 
@@ -676,7 +679,8 @@ def engine_spec(cfg) -> dict:
             "top_p": float(getattr(cfg, "local_llm_top_p", 1.0)),
             "min_p": float(getattr(cfg, "local_llm_min_p", 0.0)),
             "repetition_penalty": float(getattr(cfg, "local_llm_repetition_penalty", 1.0)),
-            "presence_penalty": float(getattr(cfg, "local_llm_presence_penalty", 0.0))}
+            "presence_penalty": float(getattr(cfg, "local_llm_presence_penalty", 0.0)),
+            "chat_template": str(getattr(cfg, "local_llm_chat_template", "auto") or "auto")}
 
 
 # ------------------------------------------------------------------ child
@@ -776,8 +780,12 @@ def worker_main() -> int:
             send({"op": "error", "msg": f"init failed: {e!r}"})
             return 3
         max_batch = model.cfg.max_batch
+    witness = _witness(dev)
+    if hasattr(eng, "chat_mode"):  # "raw" or "template:<file>": what the prompts are wrapped in
+        witness["chat_template"] = eng.chat_mode
+        LOG.info("worker %d on %s: chat template %s", os.getpid(), dev, eng.chat_mode)
     send({"op": "ready", "pid": os.getpid(), "device": dev,
-          "gpu": os.environ.get("HIP_VISIBLE_DEVICES", ""), "max_batch": max_batch, "witness": _witness(dev)})
+          "gpu": os.environ.get("HIP_VISIBLE_DEVICES", ""), "max_batch": max_batch, "witness": witness})
 
     # ONE engine stream over every session: the projects the pool deals this
     # worker share its continuous batch (MultiFeed: round-robin over them)

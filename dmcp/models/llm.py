@@ -239,11 +239,15 @@ def _checkpoint_tensor_shapes(path: str, suffixes: tuple) -> Dict[str, tuple]:
     return shapes
 
 
-def check_checkpoint(path: str) -> Optional[str]:
+def check_checkpoint(path: str, chat_template: Optional[str] = "auto") -> Optional[str]:
     """Why the checkpoint directory ``path`` cannot be loaded as the model it
     is -- naming the config key or tensor -- or None when
     :meth:`LocalLM.load_safetensors` reproduces it.  Reads ``config.json`` and
-    the safetensors headers only: no tensor data, no device."""
+    the safetensors headers only: no tensor data, no device.
+
+    ``chat_template``: the ``LOCAL_LLM_CHAT_TEMPLATE`` knob.  The chat
+    template it selects (:mod:`dmcp.enrich.chat`) is compiled and rendered
+    once; one that cannot be used is a reason too.  None: the model only."""
     cfg_path = os.path.join(path, "config.json")
     try:
         with open(cfg_path) as f:
@@ -326,6 +330,9 @@ def check_checkpoint(path: str) -> Optional[str]:
                 return f"tensor {n} has shape {list(shapes[n])}, expected [{head_dim}] (head_dim)"
     if "lm_head.weight" not in have and hf.get("tie_word_embeddings") is False:
         return "tensor lm_head.weight is missing and tie_word_embeddings is false"
+    if chat_template is not None:
+        from ..enrich.chat import template_problem
+        return template_problem(path, chat_template)
     return None
 
 
@@ -654,7 +661,7 @@ class LocalLM:
         reproduce raises :class:`CheckpointUnsupported` with the reason
         (:func:`check_checkpoint`)."""
         from safetensors.torch import load_file
-        reason = check_checkpoint(path)
+        reason = check_checkpoint(path, chat_template=None)  # the model alone: the tokenizer side is load_local_model's
         if reason is not None:
             raise CheckpointUnsupported(f"{path}: {reason}")
         with open(os.path.join(path, "config.json")) as f:

@@ -441,7 +441,8 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
                      intermediate: int = 8192, vocab: int = 128256, tokenizer: str = "code-bpe-128k",
                      outliers=(7, 300, 1029, 1800), seed: int = 11, device: str = "cuda", rope_scaling=None,
                      qkv_bias: bool = False, model_type: Optional[str] = None, tie_embeddings: bool = False,
-                     head_dim: Optional[int] = None, qk_norm: bool = False) -> str:
+                     head_dim: Optional[int] = None, qk_norm: bool = False,
+                     chat_template: Optional[str] = None) -> str:
     """A Llama-format checkpoint directory (``config.json``, one
     ``model.safetensors``, ``tokenizer.json``) with *trained-like* random
     weights -- no download exists here: heavy-tailed matrices (a Gaussian
@@ -461,7 +462,12 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
     ``k_norm`` weights [head_dim] drawn like the other norm weights (1 +- 0.25)
     after every other draw -- the Qwen3 layout; ``model_type="qwen3"`` writes
     the Qwen3 config keys (``head_dim``, ``layer_types``, ``attention_bias``,
-    ``use_sliding_window``, ``rope_theta`` 1e6)."""
+    ``use_sliding_window``, ``rope_theta`` 1e6).
+
+    ``chat_template``: a Jinja chat template (off by default: the files
+    written without it are unchanged) for the ``tokenizer.json`` of ``root``
+    -- the ``tokenizer`` asset, or with ``tokenizer=""`` a file the caller put
+    there: see :func:`write_chat_template`."""
     import gzip
     import json
 
@@ -542,6 +548,55 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
         with open(os.path.join(assets, "tokenizer_meta.json")) as f:
             meta = json.load(f)
         cfg["bos_token_id"], cfg["eos_token_id"] = meta.get("bos_token_id"), meta.get("eos_token_id")
+    if chat_template is not None:
+        bos = write_chat_template(root, chat_template, vocab)
+        if bos is not None:
+            cfg.setdefault("bos_token_id", bos)
     with open(os.path.join(root, "config.json"), "w") as f:
         json.dump(cfg, f)
     return root
+
+
+def write_chat_template(root: str, chat_template: str, vocab: int) -> Optional[int]:
+    """Makes the tokenizer of the checkpoint directory ``root`` an instruct
+    model's: every ``<|...|>`` marker of ``chat_template`` becomes a special
+    added token of ``tokenizer.json`` (a ``<|reserved_special_token_N|>``
+    entry renamed, or a new id after the last one, below ``vocab``), and
+    ``tokenizer_config.json`` gets the template, ``bos_token``
+    (``<|begin_of_text|>`` when the template emits a BOS, else none) and
+    ``eos_token`` (the template's end-of-turn marker).  Returns the BOS id."""
+    import json
+    import re
+    path = os.path.join(root, "tokenizer.json")
+    with open(path, encoding="utf-8") as f:
+        spec = json.load(f)
+    added = spec.setdefault("added_tokens", [])
+    have = {t["content"]: t for t in added}
+    markers = list(dict.fromkeys(re.findall(r"<\|[A-Za-z0-9_]+\|>", chat_template)))
+    spare = [t for t in added if t["content"].startswith("<|reserved_special_token_")]
+    next_id = max([t["id"] for t in added] + list(spec["model"]["vocab"].values())) + 1
+    for m in markers:
+        if m in have:
+            have[m]["special"] = True
+            continue
+        if spare:
+            t = spare.pop(0)
+            t["content"] = m
+        else:
+            if next_id >= vocab:
+                raise ValueError(f"no id below the vocabulary size {vocab} is left for {m}")
+            t = {"id": next_id, "content": m, "single_word": False, "lstrip": False, "rstrip": False,
+                 "normalized": False, "special": True}
+            added.append(t)
+            next_id += 1
+        have[m] = t
+    with open(path, "w", encoding="utf-8") as f:
+        json.dump(spec, f, ensure_ascii=False)
+    # a template that emits a BOS does so by name ({{ bos_token }}) or literally
+    bos = "<|begin_of_text|>" if "<|begin_of_text|>" in have and (
+        "bos_token" in chat_template or "<|begin_of_text|>" in markers) else None
+    eos = next((m for m in ("<|eot_id|>", "<|im_end|>", "<|end_of_text|>") if m in have), None)
+    with open(os.path.join(root, "tokenizer_config.json"), "w", encoding="utf-8") as f:
+        json.dump({"chat_template": chat_template, "bos_token": bos, "eos_token": eos,
+                   "add_bos_token": bos is not None, "tokenizer_class": "PreTrainedTokenizerFast"}, f)
+    return have[bos]["id"] if bos else None
