@@ -24,7 +24,7 @@ sys.path.insert(0, ROOT)
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--preset", default="dmcp-coder-1b")
-    ap.add_argument("--kv-dtype", default="fp8", choices=["bf16", "fp8"],
+    ap.add_argument("--kv-dtype", default="fp8", choices=["bf16", "fp8", "fp8s"],
                     help="KV cache storage (fp8 = e4m3, half the attention bytes)")
     ap.add_argument("--prefill-dtype", default="auto", choices=["auto", "bf16", "fp8"],
                     help="batched-prefill projections: bf16 (hipBLASLt) or fp8 (MXFP8 kernels, csrc/pgemm.hip)")

@@ -323,8 +323,9 @@ class GpuWorkerPool:
                     who.ready = True
                     who.info = msg
                     self._rebalance()
-                LOG.info("GPU worker %d ready on %s (pid %s, chat template %s)", who.index, who.device,
-                         msg.get("pid"), (msg.get("witness") or {}).get("chat_template", "n/a"))
+                wit = msg.get("witness") or {}
+                LOG.info("GPU worker %d ready on %s (pid %s, chat template %s, KV cache %s)", who.index, who.device,
+                         msg.get("pid"), wit.get("chat_template", "n/a"), wit.get("kv_dtype", "n/a"))
         if not any(w.ready and w.alive for w in self.workers):
             raise RuntimeError("no GPU worker started")
         self._initialised = True
@@ -723,24 +724,28 @@ class _EchoEngine:
             active = still
 
 
-def _witness(dev: str) -> dict:
+def _witness(dev: str, model=None) -> dict:
     """What this worker runs on, from the device itself (hipGetDeviceProperties)
     and the kernel library it loaded -- reported next to every throughput
-    number the worker produces."""
+    number the worker produces -- and, with a ``model``, its KV-cache format
+    ("kv_dtype": bf16, fp8 = unit-scale e4m3 that saturates at +-448, or fp8s =
+    per-row scaled), so a checkpoint left on the saturating default shows in
+    the log."""
+    kv = {"kv_dtype": model.cfg.kv_dtype} if model is not None else {}
     if not dev.startswith("cuda"):
-        return {"device": dev}
+        return {"device": dev, **kv}
     try:
         import torch
         p = torch.cuda.get_device_properties(0)
         out = {"name": p.name, "arch": getattr(p, "gcnArchName", ""), "cus": p.multi_processor_count,
-               "hbm_gib": round(p.total_memory / 2**30, 1)}
+               "hbm_gib": round(p.total_memory / 2**30, 1), **kv}
         from ..ops import hip
         out["hipops"] = os.path.relpath(hip.TARGET if not os.environ.get("DMCP_HIPOPS_SO") else
                                         os.environ["DMCP_HIPOPS_SO"])
         out["hipops_abi"] = int(hip.lib().dmcp_abi_version())
         return out
     except Exception as e:  # noqa: BLE001 -- a witness, never a failure
-        return {"device": dev, "error": repr(e)[:200]}
+        return {"device": dev, "error": repr(e)[:200], **kv}
 
 
 def worker_main() -> int:
@@ -768,6 +773,7 @@ def worker_main() -> int:
     if spec.get("preset") == "echo":
         eng = _EchoEngine(float(spec.get("step_s", 0.05)), int(spec.get("max_batch", 512)), int(spec.get("steps", 1)))
         max_batch = eng.max_batch
+        model = None
     else:
         import torch
         from .local import LocalEngine, build_model
@@ -780,7 +786,9 @@ def worker_main() -> int:
             send({"op": "error", "msg": f"init failed: {e!r}"})
             return 3
         max_batch = model.cfg.max_batch
-    witness = _witness(dev)
+    witness = _witness(dev, model)
+    if model is not None:
+        LOG.info("worker %d on %s: KV cache %s", os.getpid(), dev, model.cfg.kv_dtype)
     if hasattr(eng, "chat_mode"):  # "raw" or "template:<file>": what the prompts are wrapped in
         witness["chat_template"] = eng.chat_mode
         LOG.info("worker %d on %s: chat template %s", os.getpid(), dev, eng.chat_mode)

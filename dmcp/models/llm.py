@@ -83,7 +83,11 @@ class LMConfig:
     # wide steps amortise them (measured: batch 64 -> 256, 23 -> 34 classes/s)
     max_batch: int = 256
     max_rows: int = 384             # token rows per batched decode/extend step (jump-forward)
-    kv_dtype: str = "bf16"          # KV cache storage: "bf16" or "fp8" (e4m3, unit scale, half the bytes)
+    # KV cache storage: "bf16", "fp8" (e4m3, unit scale, half the bytes) or
+    # "fp8s" (e4m3 + one power-of-two exponent byte per cached row: rows that
+    # leave e4m3's range at unit scale -- Qwen2's K biases -- or sit in its
+    # subnormals keep their 3 mantissa bits; ops.reference.kv_encode_scaled)
+    kv_dtype: str = "bf16"
     # batched-prefill projections: "bf16" (hipBLASLt) or "fp8" (MXFP8
     # activations x per-row-scaled e4m3 weights on the MX matrix cores,
     # csrc/pgemm.hip, epilogues fused); decode keeps the bf16 weights.
@@ -114,10 +118,13 @@ class LMConfig:
 
     @property
     def kv_elem_bytes(self) -> int:
-        return 1 if self.kv_dtype == "fp8" else 2
+        return 1 if self.kv_dtype in ("fp8", "fp8s") else 2
 
     def kv_bytes(self) -> int:
-        return 2 * self.layers * self.max_batch * self.n_kv_heads * self.max_seq * self.head_dim * self.kv_elem_bytes
+        """The K + V slab of ``max_batch`` slots; "fp8s" counts its exponent
+        tables (one byte per cached row: 1 / head_dim of the cache)."""
+        rows = 2 * self.layers * self.max_batch * self.n_kv_heads * self.max_seq
+        return rows * self.head_dim * self.kv_elem_bytes + (rows if self.kv_dtype == "fp8s" else 0)
 
 
 PRESETS: Dict[str, LMConfig] = {
@@ -385,8 +392,11 @@ def _extend_attention(qh: torch.Tensor, k: torch.Tensor, v: torch.Tensor, start:
     return ((o1.float() * w1 + o2.float() * w2) / (w1 + w2)).to(qh.dtype)
 
 
-def _kv_bf16(t: torch.Tensor) -> torch.Tensor:
-    """A KV-cache view as bf16 (fp8 caches widened; the SDPA fallback path)."""
+def _kv_bf16(t: torch.Tensor, scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A KV-cache view as bf16 (fp8 caches widened, per-row scaled ones with
+    the same view of their exponent table; the SDPA fallback path)."""
+    if scale is not None:
+        return ops.reference.kv_decode_scaled(t, scale).to(torch.bfloat16)
     return ops.reference.kv_float(t).to(torch.bfloat16) if t.dtype == torch.uint8 else t
 
 
@@ -413,13 +423,22 @@ class LocalLM:
                  weights: Optional[Dict[str, torch.Tensor]] = None, shared_prefix: bool = True) -> None:
         if cfg.n_heads % cfg.n_kv_heads:
             raise ValueError("n_heads must be a multiple of n_kv_heads")
-        if cfg.kv_dtype not in ("bf16", "fp8"):
-            raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {cfg.kv_dtype!r}")
+        if cfg.kv_dtype not in ops.reference.KV_FORMATS:
+            raise ValueError(f"kv_dtype must be 'bf16', 'fp8' or 'fp8s', got {cfg.kv_dtype!r}")
         if cfg.prefill_dtype not in ("bf16", "fp8", "auto"):
             raise ValueError(f"prefill_dtype must be 'bf16', 'fp8' or 'auto', got {cfg.prefill_dtype!r}")
         for k in ("decode_dtype",):
             if getattr(cfg, k) not in ("bf16", "fp8"):
                 raise ValueError(f"{k} must be 'bf16' or 'fp8', got {getattr(cfg, k)!r}")
+        # the per-row scaled cache has no writer in the MXFP8 GEMM epilogues
+        self.kv_scaled = cfg.kv_dtype == "fp8s"
+        if self.kv_scaled and "fp8" in (cfg.prefill_dtype, cfg.decode_dtype):
+            raise ValueError(f"kv_dtype 'fp8s' (LOCAL_LLM_KV_DTYPE) is not written by the MXFP8 GEMMs: use "
+                             f"prefill_dtype / decode_dtype 'bf16' (LOCAL_LLM_PREFILL_DTYPE, "
+                             f"LOCAL_LLM_DECODE_DTYPE), got prefill_dtype={cfg.prefill_dtype!r} "
+                             f"decode_dtype={cfg.decode_dtype!r}")
+        if self.kv_scaled and torch.device(device).type == "cuda" and cfg.head_dim not in ops.hip.KV_SCALE_DIMS:
+            raise ValueError(f"{cfg.name}: kv_dtype 'fp8s' needs head_dim 64 or 128, got {cfg.head_dim}")
         self.cfg = cfg
         self.device = torch.device(device)
         self.dtype = torch.bfloat16
@@ -451,10 +470,16 @@ class LocalLM:
         kv_shape = (c.layers, self.num_slots, c.n_kv_heads, c.max_seq, c.head_dim)
         # fp8: OCP e4m3fn bytes in uint8 tensors, written by the RoPE/KV-append
         # kernels and widened to bf16 inside every attention kernel
-        self.kv_dtype = torch.uint8 if c.kv_dtype == "fp8" else self.dtype
+        self.kv_dtype = torch.uint8 if c.kv_dtype in ("fp8", "fp8s") else self.dtype
         self._check_kv_fits(kv_shape)
         self.k_cache = torch.zeros(kv_shape, dtype=self.kv_dtype, device=self.device)
         self.v_cache = torch.zeros(kv_shape, dtype=self.kv_dtype, device=self.device)
+        # fp8s: one exponent byte per cached row beside the caches (127 = 2^0),
+        # static buffers like them, so captured decode graphs are unaffected
+        self.k_scale = self.v_scale = None
+        if self.kv_scaled:
+            self.k_scale = torch.full(kv_shape[:-1], 127, dtype=torch.uint8, device=self.device)
+            self.v_scale = torch.full(kv_shape[:-1], 127, dtype=torch.uint8, device=self.device)
         # (a QK-norm model's table is built in fp32 like its own code's: ops.reference.rope_tables)
         self.cos_sin = ops.rope_tables(c.max_seq, c.head_dim, c.rope_theta, device=self.device,
                                        scaling=c.rope_scaling, fp32_angles=self.has_qk_norm).contiguous()
@@ -478,8 +503,12 @@ class LocalLM:
         # the attribute is cleared by tests to compare against hipBLASLt)
         # (a QK-norm model with q/k/v biases takes the weight-streaming path
         # at every row count: the two-launch small-row QKV has no bias input)
+        # (an fp8s model likewise: the fused QKV tile holds 32 of a head's
+        # columns, so it cannot take the head's amax -- without a bias its small
+        # steps run the two-launch QKV, with one the weight-streaming path)
+        two_launch = self.has_qk_norm or self.kv_scaled
         self.use_fused = (self.device.type == "cuda" and fused_shapes_ok(c)
-                          and not (self.has_qk_norm and self.has_bias))
+                          and not (two_launch and self.has_bias))
         # prefill / extend attention on the MFMA kernel (csrc/prefill_attn.hip)
         self.use_prefill_kernel = (self.device.type == "cuda"
                                    and ops.prefill_supported(c.n_heads, c.n_kv_heads, c.head_dim))
@@ -494,7 +523,7 @@ class LocalLM:
         # writes it, rope_kv normalises and rotates it), preallocated so a
         # captured step allocates nothing for it
         self.qkv_buf = (torch.empty((self.fused_max_rows, c.qkv_dim), dtype=self.dtype, device=self.device)
-                        if self.has_qk_norm and self.use_fused else None)
+                        if two_launch and self.use_fused else None)
         ps = ops.PREFIX_MFMA_MAX_SPLITS if shared_prefix else 0
         self.attn_ws = (ops.decode_workspace(self.max_rows, c.n_heads, c.n_kv_heads, c.head_dim, c.max_seq,
                                              self.device, prefix_slots=ps) if self.device.type == "cuda" else None)
@@ -542,7 +571,8 @@ class LocalLM:
             or (self.device.type == "cpu" and c.hidden % 32 == 0 and c.intermediate % 32 == 0))
         self.prefill_fp8 = fp8_ok and (c.prefill_dtype == "fp8"
                                        or (c.prefill_dtype == "auto" and self.device.type == "cuda"
-                                           and not self.has_bias and not self.has_qk_norm))
+                                           and not self.has_bias and not self.has_qk_norm
+                                           and not self.kv_scaled))
         self.decode_fp8 = c.decode_dtype == "fp8" and fp8_ok
         if "fp8" in (c.prefill_dtype, c.decode_dtype) and not fp8_ok:
             raise ValueError(f"fp8 GEMMs need head_dim 64, hidden % 2048 == 0 and a supported device "
@@ -577,14 +607,17 @@ class LocalLM:
         with a message naming the knobs, instead of an allocator OOM."""
         if self.device.type != "cuda":
             return
-        need = 2 * math.prod(kv_shape) * (1 if self.cfg.kv_dtype == "fp8" else 2)
+        need = 2 * math.prod(kv_shape) * self.cfg.kv_elem_bytes
+        if self.cfg.kv_dtype == "fp8s":
+            need += 2 * math.prod(kv_shape[:-1])  # the exponent tables
         free, total = torch.cuda.mem_get_info(self.device)
         if need + self.KV_HEADROOM > free:
             raise RuntimeError(
                 f"KV cache of {need / 2**30:.1f} GiB ({self.num_slots} slots x {self.cfg.max_seq} positions, "
                 f"{self.cfg.kv_dtype}) does not fit the {free / 2**30:.1f} GiB free of {total / 2**30:.1f} GiB on "
-                f"{self.device} (+{self.KV_HEADROOM >> 30} GiB headroom): lower LOCAL_LLM_MAX_BATCH, or use "
-                f"LOCAL_LLM_KV_DTYPE=fp8")
+                f"{self.device} (+{self.KV_HEADROOM >> 30} GiB headroom): lower LOCAL_LLM_MAX_BATCH"
+                + ("" if self.cfg.kv_dtype != "bf16" else
+                   ", or use LOCAL_LLM_KV_DTYPE=fp8 (fp8s for a checkpoint with large K biases)"))
 
     # ------------------------------------------------------------ weights
     def _init_weights(self, seed: int) -> Dict[str, torch.Tensor]:
@@ -717,6 +750,13 @@ class LocalLM:
             return None
         return self.w[f"l{i}.qnorm"], self.w[f"l{i}.knorm"], self.cfg.eps
 
+    def _kvs(self, i: int) -> Optional[tuple]:
+        """Layer i's ``kv_scale`` argument of the KV ops: its rows of the
+        exponent tables, None for the unscaled formats."""
+        if not self.kv_scaled:
+            return None
+        return self.k_scale[i], self.v_scale[i]
+
     def _mlp(self, i: int, h: torch.Tensor) -> torch.Tensor:
         gu = F.linear(h, self.w[f"l{i}.wgu"])
         return F.linear(ops.silu_mul(gu), self.w[f"l{i}.wdown"])
@@ -748,14 +788,16 @@ class LocalLM:
         for i in range(c.layers):
             kc, vc = self.k_cache[i], self.v_cache[i]
             qkv = F.linear(h, self.w[f"l{i}.wqkv"], self.w.get(f"l{i}.bqkv"))
-            q = ops.rope_kv(qkv, pos, slots, self.cos_sin, kc, vc, c.n_heads, qk_norm=self._qk_norm(i))  # [T, Hq, D]
+            kvs = self._kvs(i)
+            q = ops.rope_kv(qkv, pos, slots, self.cos_sin, kc, vc, c.n_heads, qk_norm=self._qk_norm(i),
+                            kv_scale=kvs)  # [T, Hq, D]
             if self.use_prefill_kernel:
                 att = ops.prefill_attention(q, kc, vc, slot, start_pos, self.prefix_slot if shared else None,
-                                            shared, self.scale)
+                                            shared, self.scale, kv_scale=kvs)
                 o = F.linear(att.view(T, c.n_heads * c.head_dim), self.w[f"l{i}.wo"])
             else:
-                k = _kv_bf16(kc[slot, :, :L]).unsqueeze(0)  # [1, Hkv, L, D]
-                v = _kv_bf16(vc[slot, :, :L]).unsqueeze(0)
+                k = _kv_bf16(kc[slot, :, :L], kvs[0][slot, :, :L] if kvs else None).unsqueeze(0)  # [1, Hkv, L, D]
+                v = _kv_bf16(vc[slot, :, :L], kvs[1][slot, :, :L] if kvs else None).unsqueeze(0)
                 qh = q.transpose(0, 1).unsqueeze(0)  # [1, Hq, T, D]
                 if start_pos == 0:
                     att = F.scaled_dot_product_attention(qh, k, v, is_causal=True, enable_gqa=True)
@@ -833,9 +875,11 @@ class LocalLM:
         for i in range(c.layers):
             kc, vc = self.k_cache[i], self.v_cache[i]
             qkv = F.linear(h, self.w[f"l{i}.wqkv"], self.w.get(f"l{i}.bqkv"))
+            kvs = self._kvs(i)
             q = ops.rope_kv(qkv, pos_t, slot_t, self.cos_sin, kc, vc, c.n_heads,
-                            qk_norm=self._qk_norm(i))  # [Ttot, Hq, D]
-            att = ops.prefill_attention_varlen(q, kc, vc, offsets, seq_slots, starts, prefix, shared, self.scale)
+                            qk_norm=self._qk_norm(i), kv_scale=kvs)  # [Ttot, Hq, D]
+            att = ops.prefill_attention_varlen(q, kc, vc, offsets, seq_slots, starts, prefix, shared, self.scale,
+                                               kv_scale=kvs)
             o = F.linear(att.view(Ttot, c.n_heads * c.head_dim), self.w[f"l{i}.wo"])
             h = ops.add_rmsnorm(o, self.w[f"l{i}.ln2"], c.eps, residual=resid)
             m = self._mlp(i, h)
@@ -924,18 +968,19 @@ class LocalLM:
             nxt = self.w[f"l{i + 1}.ln1"] if i + 1 < c.layers else self.w["norm_f"]
             bqkv = self.w.get(f"l{i}.bqkv")
             qkn = self._qk_norm(i)
+            kvs = self._kvs(i)
             if big:
                 q = ops.tgemm_rope_kv(h, self.w[f"l{i}.wqkv"], positions, slots, self.cos_sin, kc, vc, c.n_heads,
-                                      self.tg_ws, bias=bqkv, qk_norm=qkn)
+                                      self.tg_ws, bias=bqkv, qk_norm=qkn, kv_scale=kvs)
             elif wide:
                 q = ops.wgemm_rope_kv(h, self.w[f"l{i}.wqkv"], positions, slots, self.cos_sin, kc, vc, c.n_heads,
-                                      self.wgemm_ws, bias=bqkv, qk_norm=qkn)
+                                      self.wgemm_ws, bias=bqkv, qk_norm=qkn, kv_scale=kvs)
             else:
                 q = ops.rope_kv(F.linear(h, self.w[f"l{i}.wqkv"], bqkv), positions, slots, self.cos_sin, kc, vc,
-                                c.n_heads, qk_norm=qkn)
+                                c.n_heads, qk_norm=qkn, kv_scale=kvs)
             att = ops.decode_attention(q, kc, vc, slots, seq_len, self.scale, workspace=self.attn_ws, chunk=chunk,
-                                       fork=self.fork_tab,
-                                       prefix=self._prefix(i, prefix_rows), splits=splits).view(B, c.n_heads * c.head_dim)
+                                       fork=self.fork_tab, prefix=self._prefix(i, prefix_rows), splits=splits,
+                                       kv_scale=kvs).view(B, c.n_heads * c.head_dim)
             if big:
                 h = ops.tgemm_resid_norm(att, self.w[f"l{i}.wo"], resid, self.w[f"l{i}.ln2"], c.eps, self.tg_ws)
             elif wide:
@@ -999,6 +1044,10 @@ class LocalLM:
     def _prefix(self, i: int, rows: Optional[torch.Tensor] = None):
         if not self.shared_prefix:
             return None
+        if self.kv_scaled:
+            return ops.SharedPrefix(self.k_cache[i][self.prefix_slot], self.v_cache[i][self.prefix_slot],
+                                    self.prefix_dev, rows, self.k_scale[i][self.prefix_slot],
+                                    self.v_scale[i][self.prefix_slot])
         return ops.SharedPrefix(self.k_cache[i][self.prefix_slot], self.v_cache[i][self.prefix_slot],
                                 self.prefix_dev, rows)
 
@@ -1017,19 +1066,22 @@ class LocalLM:
                                               mask_idx, mask_alt, alt_token)
         for i in range(c.layers):
             kc, vc = self.k_cache[i], self.v_cache[i]
-            if self.has_qk_norm:
-                # the fused QKV tile holds 32 of a head's columns, so the
-                # per-head norm cannot sit in its epilogue: norm-folded QKV to
-                # a bf16 row, then the norm-taking RoPE + append (one launch
-                # more per layer; docs/KERNELS.md)
+            kvs = self._kvs(i)
+            if self.has_qk_norm or self.kv_scaled:
+                # the fused QKV tile holds 32 of a head's columns, so neither
+                # the per-head norm nor a scaled cache row's amax can sit in
+                # its epilogue: norm-folded QKV to a bf16 row, then the
+                # norm-taking / scaling RoPE + append (one launch more per
+                # layer; docs/KERNELS.md)
                 qkv = ops.fused_linear_norm(r, self.w[f"l{i}.wqkv"], c.eps, out=self.qkv_buf[:B])
-                q = ops.rope_kv(qkv, positions, slots, self.cos_sin, kc, vc, c.n_heads, qk_norm=self._qk_norm(i))
+                q = ops.rope_kv(qkv, positions, slots, self.cos_sin, kc, vc, c.n_heads, qk_norm=self._qk_norm(i),
+                                kv_scale=kvs)
             else:
                 q = ops.fused_rope_kv(r, self.w[f"l{i}.wqkv"], c.eps, positions, slots, self.cos_sin, kc, vc,
                                       c.n_heads, bias=self.w.get(f"l{i}.bqkv"))
             att = ops.decode_attention(q, kc, vc, slots, seq_len, self.scale, workspace=self.attn_ws, chunk=chunk,
                                        fork=self.fork_tab,
-                                       prefix=self._prefix(i, prefix_rows), splits=splits)
+                                       prefix=self._prefix(i, prefix_rows), splits=splits, kv_scale=kvs)
             ops.fused_resid(att.view(B, c.n_heads * c.head_dim), self.w[f"l{i}.wo"], r)
             act = ops.fused_swiglu(r, self.w[f"l{i}.wgu"], c.eps)
             ops.fused_resid(act, self.w[f"l{i}.wdown"], r)
@@ -1078,6 +1130,9 @@ class LocalLM:
         elif P:
             self.k_cache[:, slot, :, :P].copy_(self.k_cache[:, self.prefix_slot, :, :P])
             self.v_cache[:, slot, :, :P].copy_(self.v_cache[:, self.prefix_slot, :, :P])
+            if self.kv_scaled:
+                self.k_scale[:, slot, :, :P].copy_(self.k_scale[:, self.prefix_slot, :, :P])
+                self.v_scale[:, slot, :, :P].copy_(self.v_scale[:, self.prefix_slot, :, :P])
         return P
 
     @torch.inference_mode()
@@ -1092,10 +1147,11 @@ class LocalLM:
                 not (0 <= start <= end <= self.cfg.max_seq):
             raise ValueError(f"fork_kv: slot {src} -> {list(dsts)}, positions [{start}, {end})")
         if self.device.type == "cuda":  # one HIP launch for both caches (csrc/dmcp_kernels.hip kv_fork_kernel)
-            ops.hip.kv_fork(self.k_cache, self.v_cache, src, dsts, start, end)
+            ops.hip.kv_fork(self.k_cache, self.v_cache, src, dsts, start, end,
+                            (self.k_scale, self.v_scale) if self.kv_scaled else None)
             return
         idx = torch.tensor(list(dsts), dtype=torch.long, device=self.device)
-        for cache in (self.k_cache, self.v_cache):
+        for cache in (self.k_cache, self.v_cache) + ((self.k_scale, self.v_scale) if self.kv_scaled else ()):
             cache[:, idx, :, start:end] = cache[:, src, :, start:end].unsqueeze(1)
 
     @torch.inference_mode()

@@ -65,12 +65,13 @@ del _name
 
 
 def decode_attention(q, k_cache, v_cache, slot, seq_len, scale, workspace=None, chunk: int = 256, out=None,
-                     prefix=None, splits=None, fork=None):
+                     prefix=None, splits=None, fork=None, kv_scale=None):
     """Per-row decode attention; the CPU reference takes no split count."""
     if q.is_cuda:
         return hip.decode_attention(q, k_cache, v_cache, slot, seq_len, scale, workspace, chunk, out, prefix, splits,
-                                    fork)
-    return reference.decode_attention(q, k_cache, v_cache, slot, seq_len, scale, workspace, chunk, out, prefix, fork)
+                                    fork, kv_scale)
+    return reference.decode_attention(q, k_cache, v_cache, slot, seq_len, scale, workspace, chunk, out, prefix, fork,
+                                      kv_scale)
 
 
 # GPU-only fused GEMM with a shape-dependent default
@@ -84,5 +85,6 @@ def decode_plan(rows, n_kv_heads, max_seq, kv_dtype: str = "bf16"):
     An fp8 cache halves the bytes per key, so fewer, longer splits keep the
     same bytes in flight: 2,048 target waves instead of 4,096 (fp8 step 2.35
     -> 2.30 ms at 78 rows, 5.54 -> 5.36 at 320; bf16 2.84 vs 2.94 the other
-    way -- profiles/decode_target_waves_r2.txt)."""
-    return hip.decode_plan(rows, n_kv_heads, max_seq, target_waves=2048 if kv_dtype == "fp8" else 4096)
+    way -- profiles/decode_target_waves_r2.txt).  The per-row scaled format
+    ("fp8s") has fp8's bytes per key and takes fp8's plan."""
+    return hip.decode_plan(rows, n_kv_heads, max_seq, target_waves=2048 if kv_dtype in ("fp8", "fp8s") else 4096)

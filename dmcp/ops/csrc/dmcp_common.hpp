@@ -175,6 +175,80 @@ __device__ __forceinline__ int mx_exp(float amax) {
     return e < -127 ? -127 : (e > 127 ? 127 : e);
 }
 
+// ---- per-row scaled FP8 KV cache (kv_dtype fp8s, dmcp/ops/reference.py
+// kv_encode_scaled): beside the e4m3 bytes one exponent byte per cached row
+// (layer, slot, kv head, position), e + 127 with e = mx_exp(amax of the row's D
+// bf16 values); the stored element is e4m3(x * 2^-e), the decoded value
+// e4m3 * 2^(byte - 127).  Readers take ANY byte, not only the minimal one.
+// 2^(byte - 127) as a float (byte 0: the subnormal 2^-127).  Byte 255 is not
+// a scale (E8M0's NaN; 2^128 is no fp32 value): no writer produces it (e <= 120
+// for a finite amax) and a reader's result for it is undefined.
+__device__ __forceinline__ float kv_scale_f(uint32_t byte) {
+    return __uint_as_float(byte ? byte << 23 : 0x00400000u);
+}
+
+// 2^-e for a row exponent e of mx_exp (e in [-127, 120] for finite fp32 amax)
+__device__ __forceinline__ float kv_inv_scale_f(int e) { return __uint_as_float((uint32_t)(127 - e) << 23); }
+
+// 8 e4m3 bytes of a row with scale sc = kv_scale_f(byte) -> 8 bf16: the
+// conversion instruction takes the scale as an operand, so a scaled row
+// widens in as many instructions as an unscaled one, and exactly (3 mantissa
+// bits times a power of two)
+__device__ __forceinline__ uint4 fp8x8_to_bf16x8_s(const uint2& v, float sc) {
+    return make_uint4(__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.x, sc, false)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.x, sc, true)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.y, sc, false)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.y, sc, true)));
+}
+
+// The exponent of a cached row from each lane's partial amax: a head is D/8
+// consecutive lanes (8 at D = 64, 16 at D = 128) aligned to their count, in
+// the RoPE mapping (4 + 4 values a lane) and in the V mapping (8 values a
+// lane) alike -- qk_norm_quad's shuffle pattern.  Every lane of the head
+// must be active; D is 64 or 128.
+__device__ __forceinline__ int kv_head_exp(float amax, int D) {
+#pragma unroll
+    for (int m = 1; m < 8; m <<= 1) amax = fmaxf(amax, __shfl_xor(amax, m, kWave));
+    if (D == 128) amax = fmaxf(amax, __shfl_xor(amax, 8, kWave));
+    return mx_exp(amax);
+}
+
+// A K head's 4 + 4 rotated values of this lane -> bf16-rounded, scaled by the
+// head's 2^-e, as two e4m3 words; returns e
+__device__ __forceinline__ int kv_scaled_pack_k(const float* o1, const float* o2, int D, uint32_t& w1, uint32_t& w2) {
+    float r1[4], r2[4], amax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        r1[j] = bf2f(f2bf(o1[j]));
+        r2[j] = bf2f(f2bf(o2[j]));
+        amax = fmaxf(amax, fmaxf(fabsf(r1[j]), fabsf(r2[j])));
+    }
+    const int e = kv_head_exp(amax, D);
+    const float inv = kv_inv_scale_f(e);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        r1[j] *= inv;
+        r2[j] *= inv;
+    }
+    w1 = pack_fp8x4(r1);
+    w2 = pack_fp8x4(r2);
+    return e;
+}
+
+// A V head's 8 bf16 values of this lane -> scaled e4m3 bytes; returns e
+__device__ __forceinline__ int kv_scaled_pack_v(const uint4& v, int D, uint2& w) {
+    float f[8], amax = 0.f;
+    unpack8(v, f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(f[j]));
+    const int e = kv_head_exp(amax, D);
+    const float inv = kv_inv_scale_f(e);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] *= inv;
+    w = make_uint2(pack_fp8x4(f), pack_fp8x4(f + 4));
+    return e;
+}
+
 // byte address of element `off` of a bf16 or fp8 (KV8) cache
 template <bool KV8>
 __device__ __forceinline__ const void* kv_ptr(const void* base, size_t off) {

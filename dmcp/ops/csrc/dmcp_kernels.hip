@@ -20,6 +20,11 @@
 hipError_t dmcp_launch_prefix_partials(const uint16_t* q, const void* pk, const void* pv, const int32_t* plen,
                                        float* part_o, float* part_ml, int B, int Hkv, int G, int D, int ldk,
                                        int nsplit, int splits_total, float sl2, int kv8, hipStream_t st);
+// the same over a per-row scaled fp8 prefix (exponent bytes pks / pvs [Hkv, ldk])
+hipError_t dmcp_launch_prefix_partials_scaled(const uint16_t* q, const void* pk, const void* pv, const int32_t* plen,
+                                              float* part_o, float* part_ml, int B, int Hkv, int G, int D, int ldk,
+                                              int nsplit, int splits_total, float sl2, const uint8_t* pks,
+                                              const uint8_t* pvs, hipStream_t st);
 
 namespace {
 
@@ -117,8 +122,11 @@ __global__ __launch_bounds__(kBlock) void add_rmsnorm_kernel(const uint16_t* __r
 //    KV8: the caches hold fp8 e4m3 (saturated), q stays bf16
 //    QKN: per-head RMSNorm of q (weight qn [D]) and k (kn [D]) in fp32 ahead
 //         of the rotation (qk_norm_quad, dmcp_common.hpp); D is 64 or 128
+//    SC:  the per-row scaled fp8 cache (KV8 only; D 64 or 128): each K / V
+//         head's exponent byte to k_scale / v_scale [S, Hkv, MAXS], written by
+//         the first lane of the head's group (kv_scaled_pack_k / _v)
 // --------------------------------------------------------------------------
-template <bool KV8, bool QKN = false>
+template <bool KV8, bool QKN = false, bool SC = false>
 __global__ __launch_bounds__(kBlock) void rope_kv_kernel(const uint16_t* __restrict__ qkv,
                                                         const int32_t* __restrict__ pos,
                                                         const int32_t* __restrict__ slot,
@@ -129,7 +137,9 @@ __global__ __launch_bounds__(kBlock) void rope_kv_kernel(const uint16_t* __restr
                                                         int D, int max_seq, int max_pos, int num_slots,
                                                         const uint16_t* __restrict__ qn = nullptr,
                                                         const uint16_t* __restrict__ kn = nullptr,
-                                                        float eps = 0.f) {
+                                                        float eps = 0.f, uint8_t* __restrict__ k_scale = nullptr,
+                                                        uint8_t* __restrict__ v_scale = nullptr) {
+    static_assert(KV8 || !SC, "scaled caches are fp8");
     const int t = blockIdx.x;
     const int p = pos[t];
     const int s = slot[t];
@@ -161,7 +171,14 @@ __global__ __launch_bounds__(kBlock) void rope_kv_kernel(const uint16_t* __restr
         }
         if (!write_cache) continue;
         const size_t kofs = (((size_t)s * Hkv + (hh - Hq)) * max_seq + p) * D;
-        if constexpr (KV8) {
+        if constexpr (SC) {
+            uint8_t* dst = static_cast<uint8_t*>(k_cache) + kofs;
+            uint32_t w1, w2;
+            const int e = kv_scaled_pack_k(o1, o2, D, w1, w2);
+            *reinterpret_cast<uint32_t*>(dst + d0) = w1;
+            *reinterpret_cast<uint32_t*>(dst + half + d0) = w2;
+            if (d0 == 0) k_scale[((size_t)s * Hkv + (hh - Hq)) * max_seq + p] = (uint8_t)(e + 127);
+        } else if constexpr (KV8) {
             uint8_t* dst = static_cast<uint8_t*>(k_cache) + kofs;
             *reinterpret_cast<uint32_t*>(dst + d0) = pack_fp8x4_bf16r(o1);
             *reinterpret_cast<uint32_t*>(dst + half + d0) = pack_fp8x4_bf16r(o2);
@@ -179,7 +196,12 @@ __global__ __launch_bounds__(kBlock) void rope_kv_kernel(const uint16_t* __restr
         const int kh = e / D;
         const int d = e - kh * D;
         const size_t vofs = (((size_t)s * Hkv + kh) * max_seq + p) * D + d;
-        if constexpr (KV8)
+        if constexpr (SC) {
+            uint2 w;
+            const int ve = kv_scaled_pack_v(vsrc[u], D, w);
+            *reinterpret_cast<uint2*>(static_cast<uint8_t*>(v_cache) + vofs) = w;
+            if (d == 0) v_scale[((size_t)s * Hkv + kh) * max_seq + p] = (uint8_t)(ve + 127);
+        } else if constexpr (KV8)
             *reinterpret_cast<uint2*>(static_cast<uint8_t*>(v_cache) + vofs) = bf16x8_to_fp8x8(vsrc[u]);
         else
             *reinterpret_cast<uint4*>(static_cast<uint16_t*>(v_cache) + vofs) = vsrc[u];
@@ -623,14 +645,48 @@ struct KVSrc {
     const void* pk;
     const void* pv;
     int fend;  // 0: no parent
+    // per-row scaled caches (SC): the exponent bytes of the same (slot, kv
+    // head) rows, [max_seq] each; the parent's below fend
+    const uint8_t* ks = nullptr;
+    const uint8_t* vs = nullptr;
+    const uint8_t* pks = nullptr;
+    const uint8_t* pvs = nullptr;
 };
 
-template <int D, bool KV8>
-__device__ __forceinline__ void load_kv_tile(const KVSrc& src, int kt, int end, int lane, KVTile<D, KV8>& t) {
+// The exponent bytes of a tile's rows in the lanes that widen them: k[h] of
+// the lane's K row (key kt + 16h + (lane & 15)), v[r] of the row of its V
+// chunk lane + 64 r.  Empty for the unscaled formats.
+template <int D, bool SC>
+struct KVScl {};
+
+template <int D>
+struct KVScl<D, true> {
+    uint8_t k[2];
+    uint8_t v[D / 32];
+};
+
+template <int D, bool KV8, bool SC = false>
+__device__ __forceinline__ void load_kv_tile(const KVSrc& src, int kt, int end, int lane, KVTile<D, KV8>& t,
+                                             KVScl<D, SC>& sc) {
     using KRaw = std::conditional_t<KV8, uint2, uint4>;
     constexpr int VE = KV8 ? 16 : 8;  // elements per V chunk
     constexpr int CPK = D / VE;       // V chunks per key
     constexpr int NV = 32 * D / VE / kWave;
+    if constexpr (SC) {
+        // issued with the tile's K / V loads (one byte per row a lane widens),
+        // from the same source as the row: the parent below fend, keys of a
+        // partial last tile clamped to end - 1 like their rows
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int key = min(kt + 16 * h + (lane & 15), end - 1);
+            sc.k[h] = (key < src.fend ? src.pks : src.ks)[key];
+        }
+#pragma unroll
+        for (int r = 0; r < NV; ++r) {
+            const int key = min(kt + (lane + kWave * r) / CPK, end - 1);
+            sc.v[r] = (key < src.fend ? src.pvs : src.vs)[key];
+        }
+    }
     const bool par = kt + 32 <= src.fend;                // the whole tile is the parent's
     const bool mixed = !par && kt < src.fend;            // the tile straddles the fork point
     const void* kb = par ? src.pk : src.k;
@@ -703,8 +759,9 @@ __device__ __forceinline__ int vquad(int r, int q) {
 // One tile of the MFMA per-row kernel: V -> the wave's LDS tile, S^T on the
 // matrix cores, then (prefetch) the tile two ahead is loaded into the same
 // registers while the softmax and the PV product run.
-template <int D, bool KV8>
-__device__ __forceinline__ void attn_tile_mfma(KVTile<D, KV8>& cur, bool prefetch, int kt_next, const KVSrc& src,
+template <int D, bool KV8, bool SC = false>
+__device__ __forceinline__ void attn_tile_mfma(KVTile<D, KV8>& cur, KVScl<D, SC>& sc, bool prefetch, int kt_next,
+                                               const KVSrc& src,
                                                int kt, int end, int lane, int g16, uint16_t* vw,
                                                const uint16_t* tr0, int trk, int tr_half,
                                                const bf16x8_t (&qf)[D / 32], float& m, float& l,
@@ -719,9 +776,18 @@ __device__ __forceinline__ void attn_tile_mfma(KVTile<D, KV8>& cur, bool prefetc
             const int ch = lane + kWave * r;
             const int row = ch / CPK, q = 4 * (ch % CPK);
             uint16_t* rp = vw + row * D;
-            *reinterpret_cast<uint4*>(rp + 4 * vquad<D>(row, q)) = fp8x8_to_bf16x8(make_uint2(cur.v[r].x, cur.v[r].y));
-            *reinterpret_cast<uint4*>(rp + 4 * vquad<D>(row, q + 2)) =
-                fp8x8_to_bf16x8(make_uint2(cur.v[r].z, cur.v[r].w));
+            if constexpr (SC) {  // the row's 2^(byte - 127) is the conversion's scale operand
+                const float vsc = kv_scale_f(sc.v[r]);
+                *reinterpret_cast<uint4*>(rp + 4 * vquad<D>(row, q)) =
+                    fp8x8_to_bf16x8_s(make_uint2(cur.v[r].x, cur.v[r].y), vsc);
+                *reinterpret_cast<uint4*>(rp + 4 * vquad<D>(row, q + 2)) =
+                    fp8x8_to_bf16x8_s(make_uint2(cur.v[r].z, cur.v[r].w), vsc);
+            } else {
+                *reinterpret_cast<uint4*>(rp + 4 * vquad<D>(row, q)) =
+                    fp8x8_to_bf16x8(make_uint2(cur.v[r].x, cur.v[r].y));
+                *reinterpret_cast<uint4*>(rp + 4 * vquad<D>(row, q + 2)) =
+                    fp8x8_to_bf16x8(make_uint2(cur.v[r].z, cur.v[r].w));
+            }
         }
     } else {
         constexpr int CPK = D / 8;
@@ -739,14 +805,16 @@ __device__ __forceinline__ void attn_tile_mfma(KVTile<D, KV8>& cur, bool prefetc
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             bf16x8_t kf;
-            if constexpr (KV8)
+            if constexpr (SC)
+                kf = as_bf16x8(fp8x8_to_bf16x8_s(cur.k[h][ks], kv_scale_f(sc.k[h])));
+            else if constexpr (KV8)
                 kf = as_bf16x8(fp8x8_to_bf16x8(cur.k[h][ks]));
             else
                 kf = as_bf16x8(cur.k[h][ks]);
             sacc[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], sacc[h], 0, 0, 0);
         }
     }
-    if (prefetch) load_kv_tile<D, KV8>(src, kt_next, end, lane, cur);
+    if (prefetch) load_kv_tile<D, KV8, SC>(src, kt_next, end, lane, cur, sc);
     // S^T tile: register 4h+i = key kt + 16h + 4*g16 + i of query (lane&15).
     // Scale folded into one FMA per score; the key mask only on a partial
     // last tile; hardware exp2 and bf16 packing.
@@ -834,14 +902,16 @@ __device__ __forceinline__ void attn_tile_mfma(KVTile<D, KV8>& cur, bool prefetc
 //    No block-level synchronisation: each wave owns its LDS tile, so
 //    different waves of a block run different items.
 // --------------------------------------------------------------------------
-template <int D, bool KV8>
+template <int D, bool KV8, bool SC = false>
 __global__ __launch_bounds__(kBlock) void decode_attn_mfma_kernel(
     const uint16_t* __restrict__ q, const void* __restrict__ k_cache, const void* __restrict__ v_cache,
     const int32_t* __restrict__ slot, const int32_t* __restrict__ seq_len, uint16_t* __restrict__ out,
     float* __restrict__ part_o, float* __restrict__ part_ml, int B, int Hkv, int G,
     int max_seq, int chunk, int splits, float scale_log2, int num_slots, const int32_t* __restrict__ plen,
-    int ps_max, const int32_t* __restrict__ prow, const int32_t* __restrict__ fork) {
+    int ps_max, const int32_t* __restrict__ prow, const int32_t* __restrict__ fork,
+    const uint8_t* __restrict__ k_scale = nullptr, const uint8_t* __restrict__ v_scale = nullptr) {
     static_assert(D % 32 == 0, "D must be a multiple of 32");
+    static_assert(KV8 || !SC, "scaled caches are fp8");
     constexpr int KS = D / 32;    // 32-dim k-steps of the S product
     constexpr int DB = D / 16;    // 16-row d blocks of O^T
     constexpr int NW = kBlock / kWave;
@@ -902,6 +972,10 @@ __global__ __launch_bounds__(kBlock) void decode_attn_mfma_kernel(
         }
         const size_t head_off = ((size_t)s * Hkv + kh) * (size_t)max_seq * D;
         KVSrc src{kv_at<KV8>(k_cache, head_off), kv_at<KV8>(v_cache, head_off), nullptr, nullptr, 0};
+        if constexpr (SC) {  // exponent tables [S, Hkv, max_seq]
+            src.ks = k_scale + ((size_t)s * Hkv + kh) * (size_t)max_seq;
+            src.vs = v_scale + ((size_t)s * Hkv + kh) * (size_t)max_seq;
+        }
         if (fork) {  // fork[2 s] = parent slot, fork[2 s + 1] = the end of the shared keys
             const int ps = __builtin_amdgcn_readfirstlane(fork[2 * s]);
             const int fe = __builtin_amdgcn_readfirstlane(fork[2 * s + 1]);
@@ -910,6 +984,10 @@ __global__ __launch_bounds__(kBlock) void decode_attn_mfma_kernel(
                 src.pk = kv_at<KV8>(k_cache, poff);
                 src.pv = kv_at<KV8>(v_cache, poff);
                 src.fend = min(fe, L);
+                if constexpr (SC) {
+                    src.pks = k_scale + ((size_t)ps * Hkv + kh) * (size_t)max_seq;
+                    src.pvs = v_scale + ((size_t)ps * Hkv + kh) * (size_t)max_seq;
+                }
             }
         }
         float m = -1e30f, l = 0.f;
@@ -917,11 +995,12 @@ __global__ __launch_bounds__(kBlock) void decode_attn_mfma_kernel(
 #pragma unroll
         for (int db = 0; db < DB; ++db) acc[db] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         KVTile<D, KV8> ta;
-        load_kv_tile<D, KV8>(src, start, end, lane, ta);
+        KVScl<D, SC> tsc;
+        load_kv_tile<D, KV8, SC>(src, start, end, lane, ta, tsc);
         for (int t = 0; t < ntiles; ++t) {
             const int kt = start + 32 * t;
-            attn_tile_mfma<D, KV8>(ta, t + 1 < ntiles, kt + 32, src, kt, end, lane, g16, vw, tr0, trk, tr_half, qf, m, l,
-                                   acc, scale_log2);
+            attn_tile_mfma<D, KV8, SC>(ta, tsc, t + 1 < ntiles, kt + 32, src, kt, end, lane, g16, vw, tr0, trk, tr_half,
+                                       qf, m, l, acc, scale_log2);
         }
         l += __shfl_xor(l, 16, kWave);
         l += __shfl_xor(l, 32, kWave);
@@ -1046,6 +1125,27 @@ __global__ __launch_bounds__(kBlock) void kv_fork_kernel(uint8_t* __restrict__ k
     }
 }
 
+// the exponent bytes of the same positions (per-row scaled caches): tables
+// [layers][slots][Hkv][max_seq], one byte per thread
+__global__ __launch_bounds__(kBlock) void kv_fork_scale_kernel(uint8_t* __restrict__ ks, uint8_t* __restrict__ vs,
+                                                               int layers, int num_slots, int Hkv, int max_seq,
+                                                               int src, ForkDsts dsts, int ndst, int start, int span) {
+    const long per_table = (long)layers * Hkv * span;
+    const long total = 2 * per_table;
+    for (long u = (long)blockIdx.x * kBlock + threadIdx.x; u < total; u += (long)gridDim.x * kBlock) {
+        const bool isv = u >= per_table;
+        const long w = isv ? u - per_table : u;
+        const int lh = (int)(w / span), off = (int)(w - (long)lh * span);
+        const int layer = lh / Hkv, h = lh - layer * Hkv;
+        uint8_t* base = isv ? vs : ks;
+        auto at = [&](int slot) -> uint8_t* {
+            return base + (((size_t)layer * num_slots + slot) * Hkv + h) * (size_t)max_seq + start + off;
+        };
+        const uint8_t v = *at(src);
+        for (int i = 0; i < ndst; ++i) *at(dsts.d[i]) = v;
+    }
+}
+
 extern "C" {
 
 int dmcp_abi_version() { return 20; }
@@ -1103,6 +1203,28 @@ int dmcp_rope_kv_norm(const void* qkv, const void* pos, const void* slot, const 
     return hipGetLastError();
 }
 
+// dmcp_rope_kv / _norm (qn / kn nullptr = no QK-norm) appending to a per-row
+// scaled fp8 cache: k_scale / v_scale uint8 [S, Hkv, max_seq]; D is 64 or 128
+int dmcp_rope_kv_scaled(const void* qkv, const void* pos, const void* slot, const void* cos_sin, void* q_out,
+                        void* k_cache, void* v_cache, int T, int Hq, int Hkv, int D, int max_seq, int max_pos,
+                        int num_slots, void* stream, const void* qn, const void* kn, float eps, void* k_scale,
+                        void* v_scale) {
+    if (T <= 0) return 0;
+    if ((D != 64 && D != 128) || (!qn != !kn) || !k_scale || !v_scale) return hipErrorInvalidValue;
+    auto st = (hipStream_t)stream;
+    if (qn)
+        rope_kv_kernel<true, true, true><<<T, kBlock, 0, st>>>(
+            (const uint16_t*)qkv, (const int32_t*)pos, (const int32_t*)slot, (const float2*)cos_sin,
+            (uint16_t*)q_out, k_cache, v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots, (const uint16_t*)qn,
+            (const uint16_t*)kn, eps, (uint8_t*)k_scale, (uint8_t*)v_scale);
+    else
+        rope_kv_kernel<true, false, true><<<T, kBlock, 0, st>>>(
+            (const uint16_t*)qkv, (const int32_t*)pos, (const int32_t*)slot, (const float2*)cos_sin,
+            (uint16_t*)q_out, k_cache, v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots, nullptr, nullptr, 0.f,
+            (uint8_t*)k_scale, (uint8_t*)v_scale);
+    return hipGetLastError();
+}
+
 // q [B, Hq, D]; caches [S, Hkv, max_seq, D] (bf16, or fp8 e4m3 with kv8);
 // slot / seq_len [B].  With plen: every row's first *plen keys are the shared
 // prefix in prefix_k / prefix_v ([Hkv, max_seq, D], the prefix slot), read by
@@ -1111,11 +1233,14 @@ int dmcp_rope_kv_norm(const void* qkv, const void* pos, const void* slot, const 
 // combine kernel; a row that fits one split with no prefix is written directly.
 // prefix_rows (optional, int32 [B]): 0 marks a row that does not use the
 // shared prefix (its keys [0, L) are all in its own slot).
-int dmcp_decode_attention(const void* q, const void* k_cache, const void* v_cache, const void* slot,
-                          const void* seq_len, void* out, void* part_o, void* part_ml, int B, int Hq, int Hkv, int D,
-                          int max_seq, int num_slots, int chunk, int splits, float scale, const void* prefix_k,
-                          const void* prefix_v, const void* plen, int ps_max, int kv8, const void* prefix_rows,
-                          const void* fork, void* stream) {
+// k_scale / v_scale (uint8 [S, Hkv, max_seq], both or neither) and the prefix
+// slot's rows of them select the per-row scaled instantiations.
+static int decode_attention_launch(const void* q, const void* k_cache, const void* v_cache, const void* slot,
+                                   const void* seq_len, void* out, void* part_o, void* part_ml, int B, int Hq, int Hkv,
+                                   int D, int max_seq, int num_slots, int chunk, int splits, float scale,
+                                   const void* prefix_k, const void* prefix_v, const void* plen, int ps_max, int kv8,
+                                   const void* prefix_rows, const void* fork, void* stream, const uint8_t* k_scale,
+                                   const uint8_t* v_scale, const uint8_t* prefix_ks, const uint8_t* prefix_vs) {
     if (B <= 0) return 0;
     if (Hkv <= 0 || Hq % Hkv != 0 || splits <= 0 || chunk <= 0 || !(D == 64 || D == 128) || Hq / Hkv > 16)
         return hipErrorInvalidValue;
@@ -1132,8 +1257,12 @@ int dmcp_decode_attention(const void* q, const void* k_cache, const void* v_cach
     auto pl = (const int32_t*)plen;
     auto pr = prefix ? (const int32_t*)prefix_rows : nullptr;
     if (prefix) {
-        hipError_t pe = dmcp_launch_prefix_partials(qq, prefix_k, prefix_v, pl, (float*)part_o, (float*)part_ml, B,
-                                                    Hkv, G, D, max_seq, ps_max, ps_max + splits, sl2, kv8, st);
+        hipError_t pe =
+            k_scale ? dmcp_launch_prefix_partials_scaled(qq, prefix_k, prefix_v, pl, (float*)part_o, (float*)part_ml,
+                                                         B, Hkv, G, D, max_seq, ps_max, ps_max + splits, sl2,
+                                                         prefix_ks, prefix_vs, st)
+                    : dmcp_launch_prefix_partials(qq, prefix_k, prefix_v, pl, (float*)part_o, (float*)part_ml, B, Hkv,
+                                                  G, D, max_seq, ps_max, ps_max + splits, sl2, kv8, st);
         if (pe != hipSuccess) return pe;
     }
     // persistent grid: one wave per (split, row, kv head) item, a block runs
@@ -1145,20 +1274,24 @@ int dmcp_decode_attention(const void* q, const void* k_cache, const void* v_cach
     float* po = (float*)part_o;
     float* pml = (float*)part_ml;
     uint16_t* oo = (uint16_t*)out;
-#define DMCP_MFMA_DECODE(DD, K8)                                                                                   \
+#define DMCP_MFMA_DECODE(DD, K8, ...)                                                                                \
     do {                                                                                                           \
         static int per_cu = 0;                                                                                     \
         if (per_cu <= 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(                                         \
-                                &per_cu, decode_attn_mfma_kernel<DD, K8>, kBlock, 0) != hipSuccess ||           \
+                                &per_cu, decode_attn_mfma_kernel<DD, K8, ##__VA_ARGS__>, kBlock, 0) !=           \
+                                hipSuccess ||                                                                       \
                             per_cu <= 0))                                                                          \
             per_cu = 4;                                                                                            \
         const long cap = (long)per_cu * device_cu_count();                                                         \
         const dim3 wgrid((unsigned)(wblocks < cap ? wblocks : cap));                                               \
-        decode_attn_mfma_kernel<DD, K8><<<wgrid, kBlock, 0, st>>>(qq, k_cache, v_cache, sl, ln, oo, po, pml, B,   \
-                                                                  Hkv, G, max_seq, chunk, splits, sl2, num_slots, \
-                                                                  pl, ps_max, pr, (const int32_t*)fork);          \
+        decode_attn_mfma_kernel<DD, K8, ##__VA_ARGS__><<<wgrid, kBlock, 0, st>>>(                                  \
+            qq, k_cache, v_cache, sl, ln, oo, po, pml, B, Hkv, G, max_seq, chunk, splits, sl2, num_slots, pl,      \
+            ps_max, pr, (const int32_t*)fork, k_scale, v_scale);                                                   \
     } while (0)
-    if (kv8) {
+    if (k_scale) {
+        if (D == 64) DMCP_MFMA_DECODE(64, true, true);
+        else DMCP_MFMA_DECODE(128, true, true);
+    } else if (kv8) {
         if (D == 64) DMCP_MFMA_DECODE(64, true);
         else DMCP_MFMA_DECODE(128, true);
     } else {
@@ -1170,6 +1303,32 @@ int dmcp_decode_attention(const void* q, const void* k_cache, const void* v_cach
     if (e != hipSuccess || splits == 1) return e;  // every row finished in the main kernel
     return launch_combine(part_o, part_ml, sl, ln, out, B, Hq, D, max_seq, chunk, splits, num_slots, pl, ps_max, pr,
                           st);
+}
+
+int dmcp_decode_attention(const void* q, const void* k_cache, const void* v_cache, const void* slot,
+                          const void* seq_len, void* out, void* part_o, void* part_ml, int B, int Hq, int Hkv, int D,
+                          int max_seq, int num_slots, int chunk, int splits, float scale, const void* prefix_k,
+                          const void* prefix_v, const void* plen, int ps_max, int kv8, const void* prefix_rows,
+                          const void* fork, void* stream) {
+    return decode_attention_launch(q, k_cache, v_cache, slot, seq_len, out, part_o, part_ml, B, Hq, Hkv, D, max_seq,
+                                   num_slots, chunk, splits, scale, prefix_k, prefix_v, plen, ps_max, kv8, prefix_rows,
+                                   fork, stream, nullptr, nullptr, nullptr, nullptr);
+}
+
+// dmcp_decode_attention over a per-row scaled fp8 cache: k_scale / v_scale
+// uint8 [S, Hkv, max_seq]; prefix_ks / prefix_vs [Hkv, max_seq] the prefix
+// slot's rows of them (with plen)
+int dmcp_decode_attention_scaled(const void* q, const void* k_cache, const void* v_cache, const void* slot,
+                                 const void* seq_len, void* out, void* part_o, void* part_ml, int B, int Hq, int Hkv,
+                                 int D, int max_seq, int num_slots, int chunk, int splits, float scale,
+                                 const void* prefix_k, const void* prefix_v, const void* plen, int ps_max,
+                                 const void* prefix_rows, const void* fork, void* stream, const void* k_scale,
+                                 const void* v_scale, const void* prefix_ks, const void* prefix_vs) {
+    if (!k_scale || !v_scale || (plen && (!prefix_ks || !prefix_vs))) return hipErrorInvalidValue;
+    return decode_attention_launch(q, k_cache, v_cache, slot, seq_len, out, part_o, part_ml, B, Hq, Hkv, D, max_seq,
+                                   num_slots, chunk, splits, scale, prefix_k, prefix_v, plen, ps_max, 1, prefix_rows,
+                                   fork, stream, (const uint8_t*)k_scale, (const uint8_t*)v_scale,
+                                   (const uint8_t*)prefix_ks, (const uint8_t*)prefix_vs);
 }
 
 int dmcp_silu_mul(const void* gu, void* out, int T, int I, void* stream) {
@@ -1320,6 +1479,26 @@ int dmcp_kv_fork(void* k_cache, void* v_cache, int layers, int num_slots, int Hk
     const int grid = (int)std::min<long>((total + kBlock - 1) / kBlock, 4096);
     kv_fork_kernel<<<grid, kBlock, 0, (hipStream_t)stream>>>((uint8_t*)k_cache, (uint8_t*)v_cache, layers, num_slots,
                                                              Hkv, max_seq, row_bytes, src, d, ndst, start, span16);
+    return hipGetLastError();
+}
+
+// dmcp_kv_fork of a per-row scaled cache: the rows' exponent bytes (k_scale /
+// v_scale uint8 [layers, slots, Hkv, max_seq]) move with them
+int dmcp_kv_fork_scaled(void* k_cache, void* v_cache, int layers, int num_slots, int Hkv, int max_seq, int row_bytes,
+                        int src, const int32_t* dsts, int ndst, int start, int end, void* stream, void* k_scale,
+                        void* v_scale) {
+    if (end <= start || ndst <= 0) return 0;
+    if (!k_scale || !v_scale) return hipErrorInvalidValue;
+    const int rc = dmcp_kv_fork(k_cache, v_cache, layers, num_slots, Hkv, max_seq, row_bytes, src, dsts, ndst, start,
+                                end, stream);
+    if (rc != 0) return rc;  // (it validated src, dsts and the span)
+    ForkDsts d{};
+    for (int i = 0; i < ndst; ++i) d.d[i] = dsts[i];
+    const int span = end - start;
+    const long total = 2L * layers * Hkv * span;
+    const int grid = (int)std::min<long>((total + kBlock - 1) / kBlock, 4096);
+    kv_fork_scale_kernel<<<grid, kBlock, 0, (hipStream_t)stream>>>((uint8_t*)k_scale, (uint8_t*)v_scale, layers,
+                                                                   num_slots, Hkv, max_seq, src, d, ndst, start, span);
     return hipGetLastError();
 }
 

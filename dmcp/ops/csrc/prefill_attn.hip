@@ -71,15 +71,31 @@ __device__ __forceinline__ v4i16_t lds_tr16(const uint16_t* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16_t*)(p));
 }
 
+// Per-row scaled fp8 caches (SC): the exponent bytes of the slot's rows
+// ([Hkv, ldk]; pk / pv: the prefix slot's), empty for the unscaled formats --
+// their instantiations take no argument bytes and no code for it.
+template <bool SC>
+struct PfScale {};
+
+template <>
+struct PfScale<true> {
+    const uint8_t* k;
+    const uint8_t* v;
+    const uint8_t* pk;
+    const uint8_t* pv;
+};
+
 // The work of one block: kv head kh, column tile ct (32 * NSUB * NWAVE query
 // columns), key split sp of nsplit.  Shared by the single-sequence kernel,
 // the varlen (packed multi-sequence) kernel and the decode step's prefix mode.
-template <int D, int NSUB, int NWAVE, bool KV8>
+template <int D, int NSUB, int NWAVE, bool KV8, bool SC = false>
 __device__ __forceinline__ void prefill_attn_block(
     const uint16_t* __restrict__ q, const void* __restrict__ kc, const void* __restrict__ vc,
     const void* __restrict__ pk, const void* __restrict__ pv, uint16_t* __restrict__ out,
     float* __restrict__ part_o, float* __restrict__ part_ml, int T, int start, int P, int Hkv, int G, int ldk,
-    int kh, int sp, int ct, int nsplit, float sl2, const int32_t* __restrict__ plen, long prs, long pss) {
+    int kh, int sp, int ct, int nsplit, float sl2, const int32_t* __restrict__ plen, long prs, long pss,
+    PfScale<SC> ss = {}) {
+    static_assert(KV8 || !SC, "scaled caches are fp8");
     constexpr int KS = D / 16;  // k-steps of the QK product
     constexpr int DT = D / 32;  // 32-row d tiles of the PV product
     constexpr int CH = D / 8;   // 16-byte chunks per row
@@ -156,6 +172,10 @@ __device__ __forceinline__ void prefill_attn_block(
     // visible -- every such key is masked to -inf, so its P is 0.
     using Raw = std::conditional_t<KV8, uint2, uint4>;
     Raw kx[LU], vx[LU];
+    // SC: each row's exponent byte rides with its chunks (issued with the
+    // stage's loads, from the same source as the row) and becomes the scale
+    // operand of the widening conversion in store()
+    uint8_t ksx[SC ? LU : 1], vsx[SC ? LU : 1];
     auto load = [&](int st) {
 #pragma unroll
         for (int i = 0; i < LU; ++i) {
@@ -166,10 +186,17 @@ __device__ __forceinline__ void prefill_attn_block(
             const size_t off = ((size_t)kh * ldk + key) * D + ch * 8;
             kx[i] = *reinterpret_cast<const Raw*>(kv_ptr<KV8>(pre ? pk : kc, off));
             vx[i] = *reinterpret_cast<const Raw*>(kv_ptr<KV8>(pre ? pv : vc, off));
+            if constexpr (SC) {
+                const size_t so = (size_t)kh * ldk + key;
+                ksx[i] = (pre ? ss.pk : ss.k)[so];
+                vsx[i] = (pre ? ss.pv : ss.v)[so];
+            }
         }
     };
-    auto widen = [&](const Raw& v) -> uint4 {
-        if constexpr (KV8)
+    auto widen = [&](const Raw& v, uint8_t sb) -> uint4 {
+        if constexpr (SC)
+            return fp8x8_to_bf16x8_s(v, kv_scale_f(sb));
+        else if constexpr (KV8)
             return fp8x8_to_bf16x8(v);
         else
             return v;
@@ -179,8 +206,13 @@ __device__ __forceinline__ void prefill_attn_block(
         for (int i = 0; i < LU; ++i) {
             const int idx = threadIdx.x + i * NT;
             const int row = idx / CH, ch = idx - row * CH;
-            *reinterpret_cast<uint4*>(&sK[buf][pf_off<D>(row, ch)]) = widen(kx[i]);
-            *reinterpret_cast<uint4*>(&sV[buf][pf_off<D>(row, ch)]) = widen(vx[i]);
+            if constexpr (SC) {
+                *reinterpret_cast<uint4*>(&sK[buf][pf_off<D>(row, ch)]) = widen(kx[i], ksx[i]);
+                *reinterpret_cast<uint4*>(&sV[buf][pf_off<D>(row, ch)]) = widen(vx[i], vsx[i]);
+            } else {
+                *reinterpret_cast<uint4*>(&sK[buf][pf_off<D>(row, ch)]) = widen(kx[i], 127);
+                *reinterpret_cast<uint4*>(&sV[buf][pf_off<D>(row, ch)]) = widen(vx[i], 127);
+            }
         }
     };
 
@@ -337,18 +369,18 @@ __device__ __forceinline__ void prefill_attn_block(
     }
 }
 
-template <int D, int NSUB, int NWAVE, bool KV8>
+template <int D, int NSUB, int NWAVE, bool KV8, bool SC = false>
 __global__ __launch_bounds__(NWAVE * 64) void prefill_attn_kernel(
     const uint16_t* __restrict__ q, const void* __restrict__ kc, const void* __restrict__ vc,
     const void* __restrict__ pk, const void* __restrict__ pv, uint16_t* __restrict__ out,
     float* __restrict__ part_o, float* __restrict__ part_ml, int T, int start, int P, int Hkv, int G, int ldk,
-    int ctiles, int nsplit, float sl2, const int32_t* __restrict__ plen, long prs, long pss) {
+    int ctiles, int nsplit, float sl2, const int32_t* __restrict__ plen, long prs, long pss, PfScale<SC> ss) {
     const int kh = blockIdx.x % Hkv;
     const int rest = (int)(blockIdx.x / Hkv);
     const int sp = rest % nsplit;
     const int ct = ctiles - 1 - rest / nsplit;  // heavy (late) column tiles first
-    prefill_attn_block<D, NSUB, NWAVE, KV8>(q, kc, vc, pk, pv, out, part_o, part_ml, T, start, P, Hkv, G, ldk, kh, sp,
-                                            ct, nsplit, sl2, plen, prs, pss);
+    prefill_attn_block<D, NSUB, NWAVE, KV8, SC>(q, kc, vc, pk, pv, out, part_o, part_ml, T, start, P, Hkv, G, ldk, kh,
+                                                sp, ct, nsplit, sl2, plen, prs, pss, ss);
 }
 
 // Packed multi-sequence prefill (the engine's batched admission): q / out
@@ -357,12 +389,12 @@ __global__ __launch_bounds__(NWAVE * 64) void prefill_attn_kernel(
 // descending key count so the long tiles start first, for kv head b % Hkv.
 // seq[i] = (token offset, T, start, slot, shared-prefix length).  No split-K:
 // a batch of 2,000-token prompts is thousands of blocks already.
-template <int D, int NSUB, int NWAVE, bool KV8>
+template <int D, int NSUB, int NWAVE, bool KV8, bool SC = false>
 __global__ __launch_bounds__(NWAVE * 64) void prefill_varlen_kernel(
     const uint16_t* __restrict__ q, const void* __restrict__ kcache, const void* __restrict__ vcache,
     const void* __restrict__ pk, const void* __restrict__ pv, uint16_t* __restrict__ out,
     const int32_t* __restrict__ items, const int32_t* __restrict__ seq, int Hkv, int G, int ldk, size_t slot_elems,
-    float sl2) {
+    float sl2, PfScale<SC> ss) {
     const int kh = blockIdx.x % Hkv;
     const int it = blockIdx.x / Hkv;
     const int si = items[2 * it], ct = items[2 * it + 1];
@@ -372,8 +404,17 @@ __global__ __launch_bounds__(NWAVE * 64) void prefill_varlen_kernel(
     const size_t kvoff = (size_t)slot * slot_elems * (KV8 ? 1 : 2);
     const void* kc = static_cast<const char*>(kcache) + kvoff;
     const void* vc = static_cast<const char*>(vcache) + kvoff;
-    prefill_attn_block<D, NSUB, NWAVE, KV8>(q + row0, kc, vc, P > 0 ? pk : kc, P > 0 ? pv : vc, out + row0, nullptr,
-                                            nullptr, T, start, P, Hkv, G, ldk, kh, 0, ct, 1, sl2, nullptr, 1L, 1L);
+    if constexpr (SC) {  // ss.k / ss.v: the whole tables [S, Hkv, ldk]; this sequence's slot rows
+        ss.k += (size_t)slot * Hkv * ldk;
+        ss.v += (size_t)slot * Hkv * ldk;
+        if (P <= 0) {
+            ss.pk = ss.k;
+            ss.pv = ss.v;
+        }
+    }
+    prefill_attn_block<D, NSUB, NWAVE, KV8, SC>(q + row0, kc, vc, P > 0 ? pk : kc, P > 0 ? pv : vc, out + row0, nullptr,
+                                                nullptr, T, start, P, Hkv, G, ldk, kh, 0, ct, 1, sl2, nullptr, 1L, 1L,
+                                                ss);
 }
 
 // split-K merge: out[row, :] = sum_s O_s exp2(m_s - M) / sum_s l_s exp2(m_s - M),
@@ -405,15 +446,15 @@ __global__ __launch_bounds__(kBlock) void prefill_combine_kernel(const float* __
     *reinterpret_cast<uint2*>(out + row * D + d) = pack4(f);
 }
 
-template <int D, int NSUB, int NWAVE, bool KV8>
+template <int D, int NSUB, int NWAVE, bool KV8, bool SC = false>
 hipError_t launch_prefill(const uint16_t* q, const void* k, const void* v, const void* pk, const void* pv,
                           uint16_t* out, float* po, float* pml, int T, int start, int P, int Hkv, int G, int ldk,
-                          int nsplit, float sl2, hipStream_t st) {
+                          int nsplit, float sl2, hipStream_t st, PfScale<SC> ss = {}) {
     constexpr int COLS = 32 * NSUB * NWAVE;
     const int ctiles = (T * G + COLS - 1) / COLS;
-    prefill_attn_kernel<D, NSUB, NWAVE, KV8><<<dim3((unsigned)(ctiles * Hkv * nsplit)), NWAVE * kWave, 0, st>>>(
+    prefill_attn_kernel<D, NSUB, NWAVE, KV8, SC><<<dim3((unsigned)(ctiles * Hkv * nsplit)), NWAVE * kWave, 0, st>>>(
         q, k, v, pk, pv, out, po, pml, T, start, P, Hkv, G, ldk, ctiles, nsplit, sl2, nullptr, 1L,
-        (long)T * G * Hkv);
+        (long)T * G * Hkv, ss);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || nsplit == 1) return e;
     const int rows = T * G * Hkv;
@@ -440,13 +481,36 @@ hipError_t dmcp_launch_prefix_partials(const uint16_t* q, const void* pk, const 
 #define DMCP_PFX(DD, K8)                                                                                          \
     prefill_attn_kernel<DD, 1, 4, K8><<<grid, 4 * kWave, 0, st>>>(q, pk, pv, pk, pv, nullptr, part_o, part_ml, B,    \
                                                                  ldk, 0, Hkv, G, ldk, ctiles, nsplit, sl2, plen,   \
-                                                                 (long)splits_total, 1L)
+                                                                 (long)splits_total, 1L, PfScale<false>{})
     if (D == 64 && kv8) DMCP_PFX(64, true);
     else if (D == 64) DMCP_PFX(64, false);
     else if (D == 128 && kv8) DMCP_PFX(128, true);
     else if (D == 128) DMCP_PFX(128, false);
     else return hipErrorInvalidValue;
 #undef DMCP_PFX
+    return hipGetLastError();
+}
+
+// ... over a per-row scaled fp8 prefix: pks / pvs [Hkv, ldk] exponent bytes
+hipError_t dmcp_launch_prefix_partials_scaled(const uint16_t* q, const void* pk, const void* pv, const int32_t* plen,
+                                              float* part_o, float* part_ml, int B, int Hkv, int G, int D, int ldk,
+                                              int nsplit, int splits_total, float sl2, const uint8_t* pks,
+                                              const uint8_t* pvs, hipStream_t st) {
+    constexpr int COLS = 32 * 4;
+    const int ctiles = (B * G + COLS - 1) / COLS;
+    const dim3 grid((unsigned)(ctiles * Hkv * nsplit));
+    if (!pks || !pvs) return hipErrorInvalidValue;
+    const PfScale<true> ss{pks, pvs, pks, pvs};
+    if (D == 64)
+        prefill_attn_kernel<64, 1, 4, true, true><<<grid, 4 * kWave, 0, st>>>(
+            q, pk, pv, pk, pv, nullptr, part_o, part_ml, B, ldk, 0, Hkv, G, ldk, ctiles, nsplit, sl2, plen,
+            (long)splits_total, 1L, ss);
+    else if (D == 128)
+        prefill_attn_kernel<128, 1, 4, true, true><<<grid, 4 * kWave, 0, st>>>(
+            q, pk, pv, pk, pv, nullptr, part_o, part_ml, B, ldk, 0, Hkv, G, ldk, ctiles, nsplit, sl2, plen,
+            (long)splits_total, 1L, ss);
+    else
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -523,13 +587,74 @@ int dmcp_prefill_varlen(const void* q, const void* kc, const void* vc, const voi
 #define DMCP_PV(DD, K8)                                                                                         \
     prefill_varlen_kernel<DD, 1, 4, K8><<<grid, 4 * kWave, 0, st>>>((const uint16_t*)q, kc, vc, pk, pv,           \
                                                                     (uint16_t*)out, it, sq, Hkv, G, ldk,          \
-                                                                    (size_t)slot_elems, sl2)
+                                                                    (size_t)slot_elems, sl2, PfScale<false>{})
     if (D == 64 && kv8) DMCP_PV(64, true);
     else if (D == 64) DMCP_PV(64, false);
     else if (D == 128 && kv8) DMCP_PV(128, true);
     else if (D == 128) DMCP_PV(128, false);
     else return hipErrorInvalidValue;
 #undef DMCP_PV
+    return hipGetLastError();
+}
+
+// dmcp_prefill_attention over a per-row scaled fp8 cache: ks / vs the slot's
+// exponent bytes [Hkv, ldk], pks / pvs the prefix slot's (P > 0)
+int dmcp_prefill_attention_scaled(const void* q, const void* k, const void* v, const void* pk, const void* pv,
+                                  void* out, void* part_o, void* part_ml, int T, int start, int P, int Hq, int Hkv,
+                                  int D, int ldk, float scale, int variant, int nsplit, void* stream, const void* ks,
+                                  const void* vs, const void* pks, const void* pvs) {
+    if (T <= 0) return 0;
+    if (!q || !k || !v || !out || Hkv <= 0 || Hq % Hkv != 0 || start < 0 || P < 0 || P > start ||
+        start + T > ldk || (P > 0 && (!pk || !pv || !pks || !pvs)) || nsplit < 1 || nsplit > 64 ||
+        (nsplit > 1 && (!part_o || !part_ml)) || !ks || !vs)
+        return hipErrorInvalidValue;
+    if ((long)T * Hq > (1L << 28)) return hipErrorInvalidValue;
+    const int G = Hq / Hkv;
+    const float sl2 = scale * 1.4426950408889634f;
+    auto st = (hipStream_t)stream;
+    auto qq = (const uint16_t*)q;
+    const void* ppk = P > 0 ? pk : k;
+    const void* ppv = P > 0 ? pv : v;
+    const PfScale<true> ss{(const uint8_t*)ks, (const uint8_t*)vs, (const uint8_t*)(P > 0 ? pks : ks),
+                           (const uint8_t*)(P > 0 ? pvs : vs)};
+    auto oo = (uint16_t*)out;
+    auto po = (float*)part_o;
+    auto pml = (float*)part_ml;
+#define DMCP_PFS(DD, NW) \
+    launch_prefill<DD, 1, NW, true, true>(qq, k, v, ppk, ppv, oo, po, pml, T, start, P, Hkv, G, ldk, nsplit, sl2, st, ss)
+    if (D == 64 && variant == 0) return DMCP_PFS(64, 4);
+    if (D == 64 && variant == 1) return DMCP_PFS(64, 8);
+    if (D == 128 && variant == 0) return DMCP_PFS(128, 4);
+    if (D == 128 && variant == 1) return DMCP_PFS(128, 8);
+#undef DMCP_PFS
+    return hipErrorInvalidValue;
+}
+
+// dmcp_prefill_varlen over a per-row scaled fp8 cache: ks / vs the exponent
+// tables [S, Hkv, ldk], pks / pvs the prefix slot's rows of them
+int dmcp_prefill_varlen_scaled(const void* q, const void* kc, const void* vc, const void* pk, const void* pv,
+                               void* out, const void* items, const void* seq, int nitems, int Hq, int Hkv, int D,
+                               int ldk, long slot_elems, float scale, void* stream, const void* ks, const void* vs,
+                               const void* pks, const void* pvs) {
+    if (nitems <= 0) return 0;
+    if (!q || !kc || !vc || !out || !items || !seq || Hkv <= 0 || Hq % Hkv != 0 ||
+        (long)nitems * Hkv > (1L << 31) || !ks || !vs || (!pk != !pks) || (!pv != !pvs))
+        return hipErrorInvalidValue;
+    const int G = Hq / Hkv;
+    const float sl2 = scale * 1.4426950408889634f;
+    const dim3 grid((unsigned)(nitems * Hkv));
+    auto st = (hipStream_t)stream;
+    auto it = (const int32_t*)items;
+    auto sq = (const int32_t*)seq;
+    const PfScale<true> ss{(const uint8_t*)ks, (const uint8_t*)vs, (const uint8_t*)pks, (const uint8_t*)pvs};
+    if (D == 64)
+        prefill_varlen_kernel<64, 1, 4, true, true><<<grid, 4 * kWave, 0, st>>>(
+            (const uint16_t*)q, kc, vc, pk, pv, (uint16_t*)out, it, sq, Hkv, G, ldk, (size_t)slot_elems, sl2, ss);
+    else if (D == 128)
+        prefill_varlen_kernel<128, 1, 4, true, true><<<grid, 4 * kWave, 0, st>>>(
+            (const uint16_t*)q, kc, vc, pk, pv, (uint16_t*)out, it, sq, Hkv, G, ldk, (size_t)slot_elems, sl2, ss);
+    else
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -109,13 +109,16 @@ __global__ __launch_bounds__(kBlock) void reduce_resid_norm_kernel(const float* 
 // (slot[t], :, pos[t], :) -- dmcp_kernels.hip::rope_kv_kernel over an LDS row
 // of the bf16-rounded sum (what F.linear + rope_kv compute).  QKN: the
 // per-head q / k RMSNorm (qk_norm_quad) on the bf16 row ahead of the rotation.
-template <bool KV8, bool QKN = false>
+// SC: the per-row scaled fp8 cache (KV8 only; D 64 or 128), as rope_kv_kernel's.
+template <bool KV8, bool QKN = false, bool SC = false>
 __global__ __launch_bounds__(kBlock) void reduce_rope_kv_kernel(
     const float* __restrict__ part, int S, int M, const int32_t* __restrict__ pos, const int32_t* __restrict__ slot,
     const float2* __restrict__ cos_sin, uint16_t* __restrict__ q_out, void* __restrict__ k_cache,
     void* __restrict__ v_cache, int Hq, int Hkv, int D, int max_seq, int max_pos, int num_slots,
     const uint16_t* __restrict__ bias, const uint16_t* __restrict__ qn = nullptr,
-    const uint16_t* __restrict__ kn = nullptr, float eps = 0.f) {
+    const uint16_t* __restrict__ kn = nullptr, float eps = 0.f, uint8_t* __restrict__ k_scale = nullptr,
+    uint8_t* __restrict__ v_scale = nullptr) {
+    static_assert(KV8 || !SC, "scaled caches are fp8");
     __shared__ uint4 rowbuf[8192 / 8];
     const int t = blockIdx.x;
     const int N = (Hq + 2 * Hkv) * D;
@@ -162,7 +165,14 @@ __global__ __launch_bounds__(kBlock) void reduce_rope_kv_kernel(
         }
         if (!write_cache) continue;
         const size_t kofs = (((size_t)sl * Hkv + (hh - Hq)) * max_seq + p) * D;
-        if constexpr (KV8) {
+        if constexpr (SC) {
+            uint8_t* dst = static_cast<uint8_t*>(k_cache) + kofs;
+            uint32_t w1, w2;
+            const int e = kv_scaled_pack_k(o1, o2, D, w1, w2);
+            *reinterpret_cast<uint32_t*>(dst + d0) = w1;
+            *reinterpret_cast<uint32_t*>(dst + half + d0) = w2;
+            if (d0 == 0) k_scale[((size_t)sl * Hkv + (hh - Hq)) * max_seq + p] = (uint8_t)(e + 127);
+        } else if constexpr (KV8) {
             uint8_t* dst = static_cast<uint8_t*>(k_cache) + kofs;
             *reinterpret_cast<uint32_t*>(dst + d0) = pack_fp8x4_bf16r(o1);
             *reinterpret_cast<uint32_t*>(dst + half + d0) = pack_fp8x4_bf16r(o2);
@@ -180,7 +190,12 @@ __global__ __launch_bounds__(kBlock) void reduce_rope_kv_kernel(
         const int kh = e / D;
         const int d = e - kh * D;
         const size_t vofs = (((size_t)sl * Hkv + kh) * max_seq + p) * D + d;
-        if constexpr (KV8)
+        if constexpr (SC) {
+            uint2 w;
+            const int ve = kv_scaled_pack_v(vsrc[uu], D, w);
+            *reinterpret_cast<uint2*>(static_cast<uint8_t*>(v_cache) + vofs) = w;
+            if (d == 0) v_scale[((size_t)sl * Hkv + kh) * max_seq + p] = (uint8_t)(ve + 127);
+        } else if constexpr (KV8)
             *reinterpret_cast<uint2*>(static_cast<uint8_t*>(v_cache) + vofs) = bf16x8_to_fp8x8(vsrc[uu]);
         else
             *reinterpret_cast<uint4*>(static_cast<uint16_t*>(v_cache) + vofs) = vsrc[uu];
@@ -311,6 +326,33 @@ int dmcp_reduce_rope_kv_norm(const void* part, int S, const void* pos, const voi
         reduce_rope_kv_kernel<false, true><<<M, kBlock, 0, st>>>(
             pp, S, M, (const int32_t*)pos, (const int32_t*)slot, (const float2*)cos_sin, (uint16_t*)q_out, k_cache,
             v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots, bb, (const uint16_t*)qn, (const uint16_t*)kn, eps);
+    return hipGetLastError();
+}
+
+// dmcp_reduce_rope_kv / _norm (qn / kn nullptr = no QK-norm) appending to a
+// per-row scaled fp8 cache: k_scale / v_scale uint8 [S, Hkv, max_seq]; D is 64
+// or 128
+int dmcp_reduce_rope_kv_scaled(const void* part, int S, const void* pos, const void* slot, const void* cos_sin,
+                               void* q_out, void* k_cache, void* v_cache, int M, int Hq, int Hkv, int D, int max_seq,
+                               int max_pos, int num_slots, void* stream, const void* bias, const void* qn,
+                               const void* kn, float eps, void* k_scale, void* v_scale) {
+    if (M <= 0) return 0;
+    if (!part || S < 1 || (D != 64 && D != 128) || (Hq + 2 * Hkv) * D > 8192 || !pos || !slot || !cos_sin ||
+        !q_out || !k_cache || !v_cache || max_pos <= 0 || (!qn != !kn) || !k_scale || !v_scale)
+        return hipErrorInvalidValue;
+    auto st = (hipStream_t)stream;
+    auto pp = (const float*)part;
+    auto bb = (const uint16_t*)bias;  // [N] bf16 or nullptr
+    if (qn)
+        reduce_rope_kv_kernel<true, true, true><<<M, kBlock, 0, st>>>(
+            pp, S, M, (const int32_t*)pos, (const int32_t*)slot, (const float2*)cos_sin, (uint16_t*)q_out, k_cache,
+            v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots, bb, (const uint16_t*)qn, (const uint16_t*)kn, eps,
+            (uint8_t*)k_scale, (uint8_t*)v_scale);
+    else
+        reduce_rope_kv_kernel<true, false, true><<<M, kBlock, 0, st>>>(
+            pp, S, M, (const int32_t*)pos, (const int32_t*)slot, (const float2*)cos_sin, (uint16_t*)q_out, k_cache,
+            v_cache, Hq, Hkv, D, max_seq, max_pos, num_slots, bb, nullptr, nullptr, 0.f, (uint8_t*)k_scale,
+            (uint8_t*)v_scale);
     return hipGetLastError();
 }
 

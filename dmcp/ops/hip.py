@@ -120,6 +120,19 @@ def lib() -> ctypes.CDLL:
             "dmcp_history_mark": ([_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp], _i),
             # history, words per row, n_slots, host int array of slots, its length
             "dmcp_history_reset": ([_vp, _i, _i, _vp, _i, _vp], _i),
+            # the per-row scaled fp8 cache (kv_scale=): the unscaled siblings' lists without kv8, the QK-norm
+            # weights + eps where the sibling has a _norm form, then the exponent tables (k, v[, prefix k, v])
+            "dmcp_rope_kv_scaled": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f,
+                                     _vp, _vp], _i),
+            "dmcp_reduce_rope_kv_scaled": ([_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp,
+                                            _vp, _vp, _vp, _f, _vp, _vp], _i),
+            "dmcp_decode_attention_scaled": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i,
+                                              _f, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+            "dmcp_prefill_attention_scaled": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f,
+                                               _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
+            "dmcp_prefill_varlen_scaled": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_long,
+                                            _f, _vp, _vp, _vp, _vp, _vp], _i),
+            "dmcp_kv_fork_scaled": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp], _i),
         }
         for name, (args, res) in sigs.items():
             try:
@@ -174,6 +187,32 @@ def _req_kv(k_cache: torch.Tensor, v_cache: torch.Tensor, name: str) -> int:
     if v_cache.shape != k_cache.shape:
         raise HipOpsError(f"{name}: k/v cache shapes differ")
     return int(k_cache.dtype == torch.uint8)
+
+
+KV_SCALE_DIMS = (64, 128)  # head sizes whose lane groups (D / 8 lanes a head) the scaled writers reduce over
+
+
+def _req_kv_scale(kv_scale: Optional[tuple], k_cache: torch.Tensor, name: str) -> Optional[tuple]:
+    """The exponent tables ``(k_scale, v_scale)`` of a per-row scaled fp8 cache
+    (dmcp.ops.reference.kv_encode_scaled), checked before any launch: fp8
+    caches of head_dim 64 or 128, and two contiguous uint8 tensors of the
+    caches' shape without the last axis on their device.  None passes."""
+    if kv_scale is None:
+        return None
+    if not isinstance(kv_scale, (tuple, list)) or len(kv_scale) != 2:
+        raise HipOpsError(f"{name}: kv_scale must be (k_scale, v_scale)")
+    if k_cache.dtype != torch.uint8:
+        raise HipOpsError(f"{name}: kv_scale needs fp8 (uint8) caches, got {k_cache.dtype}")
+    if k_cache.shape[-1] not in KV_SCALE_DIMS:
+        raise HipOpsError(f"{name}: kv_scale needs head_dim in {KV_SCALE_DIMS}, got {k_cache.shape[-1]}")
+    for t, which in zip(kv_scale, ("k_scale", "v_scale")):
+        if not isinstance(t, torch.Tensor):
+            raise HipOpsError(f"{name}.{which}: expected a tensor")
+        _req(t, torch.uint8, f"{name}.{which}")
+        if tuple(t.shape) != tuple(k_cache.shape[:-1]) or t.device != k_cache.device:
+            raise HipOpsError(f"{name}.{which}: shape {tuple(t.shape)} on {t.device}, the caches need "
+                              f"{tuple(k_cache.shape[:-1])} on {k_cache.device}")
+    return kv_scale[0], kv_scale[1]
 
 
 def _req_out(t: torch.Tensor, dtype: torch.dtype, numel: int, name: str) -> None:
@@ -240,10 +279,11 @@ def add_rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float, residual: Opt
 
 def rope_kv(qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
             k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, q_out: Optional[torch.Tensor] = None,
-            qk_norm: Optional[tuple] = None) -> torch.Tensor:
+            qk_norm: Optional[tuple] = None, kv_scale: Optional[tuple] = None) -> torch.Tensor:
     """k_cache/v_cache: [S, Hkv, MAXS, D]; returns q [T, Hq, D].  ``qk_norm``
     (q_weight [D], k_weight [D], eps): per-head RMSNorm of q and k in fp32
-    ahead of the rotation (D 64 or 128)."""
+    ahead of the rotation (D 64 or 128).  ``kv_scale`` (k_scale, v_scale uint8
+    [S, Hkv, MAXS]): append in the per-row scaled fp8 format (D 64 or 128)."""
     S, Hkv, MAXS, D = k_cache.shape
     T = qkv.shape[0]
     _req(qkv, torch.bfloat16, "rope_kv.qkv")
@@ -262,6 +302,14 @@ def rope_kv(qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: t
         q_out = torch.empty((T, n_q_heads, D), dtype=torch.bfloat16, device=qkv.device)
     _req_out(q_out, torch.bfloat16, T * n_q_heads * D, "rope_kv.q_out")
     qk_norm = _req_qk_norm(qk_norm, D, "rope_kv")
+    kv_scale = _req_kv_scale(kv_scale, k_cache, "rope_kv")
+    if kv_scale is not None:
+        qw, kw, neps = qk_norm if qk_norm is not None else (None, None, 0.0)
+        _check(lib().dmcp_rope_kv_scaled(_ptr(qkv), _ptr(pos), _ptr(slot), _ptr(cos_sin), _ptr(q_out),
+                                         _ptr(k_cache), _ptr(v_cache), T, n_q_heads, Hkv, D, MAXS, max_pos, S,
+                                         _stream(), _ptr(qw), _ptr(kw), neps, _ptr(kv_scale[0]),
+                                         _ptr(kv_scale[1])), "dmcp_rope_kv_scaled")
+        return q_out
     if qk_norm is not None:
         qw, kw, neps = qk_norm
         _check(lib().dmcp_rope_kv_norm(_ptr(qkv), _ptr(pos), _ptr(slot), _ptr(cos_sin), _ptr(q_out), _ptr(k_cache),
@@ -312,8 +360,12 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
                      seq_len: torch.Tensor, scale: float, workspace: Optional[tuple] = None,
                      chunk: int = 256, out: Optional[torch.Tensor] = None,
                      prefix: Optional["SharedPrefix"] = None, splits: Optional[int] = None,
-                     fork: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     fork: Optional[torch.Tensor] = None, kv_scale: Optional[tuple] = None) -> torch.Tensor:
     """q [B, Hq, D]; caches [S, Hkv, MAXS, D]; slot/seq_len int32 [B].
+
+    ``kv_scale`` (k_scale, v_scale uint8 [S, Hkv, MAXS]): the caches are
+    per-row scaled fp8; a shared prefix then carries its slot's rows of the
+    tables (``prefix.k_scale`` / ``prefix.v_scale`` [Hkv, MAXS]).
 
     ``fork`` (int32 [S, 2], optional): per slot (parent slot, end) -- a
     method branch reads its keys below ``end`` from its class head's slot in
@@ -336,6 +388,16 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     S, Hkv, MAXS, Dk = k_cache.shape
     _req(q, torch.bfloat16, "decode_attention.q")
     kv8 = _req_kv(k_cache, v_cache, "decode_attention")
+    kv_scale = _req_kv_scale(kv_scale, k_cache, "decode_attention")
+    pks = pvs = None
+    if kv_scale is not None and prefix is not None:
+        pks, pvs = getattr(prefix, "k_scale", None), getattr(prefix, "v_scale", None)
+        for t, which in ((pks, "k_scale"), (pvs, "v_scale")):
+            if not isinstance(t, torch.Tensor):
+                raise HipOpsError(f"decode_attention: a scaled cache's prefix needs prefix.{which}")
+            _req(t, torch.uint8, f"decode_attention.prefix.{which}")
+            if tuple(t.shape) != (Hkv, MAXS):
+                raise HipOpsError(f"decode_attention.prefix.{which}: shape {tuple(t.shape)}, expected {(Hkv, MAXS)}")
     _req(slot, torch.int32, "decode_attention.slot")
     _req(seq_len, torch.int32, "decode_attention.seq_len")
     if Dk != D or D not in (64, 128) or Hq % Hkv or (Hq // Hkv) not in (1, 2, 3, 4, 6, 8) or v_cache.shape != k_cache.shape:
@@ -383,6 +445,14 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
             raise HipOpsError("decode_attention: workspace too small")
     else:
         part_o = part_ml = None
+    if kv_scale is not None:
+        _check(lib().dmcp_decode_attention_scaled(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(slot), _ptr(seq_len),
+                                                  _ptr(out), _ptr(part_o), _ptr(part_ml), B, Hq, Hkv, D, MAXS, S,
+                                                  chunk, splits, float(scale), _ptr(pk), _ptr(pv), _ptr(plen), ps_max,
+                                                  _ptr(prows), _ptr(fork), _stream(), _ptr(kv_scale[0]),
+                                                  _ptr(kv_scale[1]), _ptr(pks), _ptr(pvs)),
+               "dmcp_decode_attention_scaled")
+        return out
     _check(lib().dmcp_decode_attention(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(slot), _ptr(seq_len), _ptr(out),
                                        _ptr(part_o), _ptr(part_ml), B, Hq, Hkv, D, MAXS, S, chunk, splits,
                                        float(scale), _ptr(pk), _ptr(pv), _ptr(plen), ps_max, kv8, _ptr(prows),
@@ -409,18 +479,21 @@ def prefill_splits(T: int, Hq: int, Hkv: int, variant: int = 0, target_blocks: i
 
 def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slot: int, start: int,
                       prefix_slot: Optional[int] = None, prefix_len: int = 0, scale: float = 1.0,
-                      out: Optional[torch.Tensor] = None, variant: int = 0, nsplit: int = 0) -> torch.Tensor:
+                      out: Optional[torch.Tensor] = None, variant: int = 0, nsplit: int = 0,
+                      kv_scale: Optional[tuple] = None) -> torch.Tensor:
     """Causal attention of q [T, Hq, D] (positions [start, start+T) of
     ``slot``, K/V already appended by rope_kv) over keys [0, start+T) of the
     caches [S, Hkv, MAXS, D]; keys [0, prefix_len) are read in place from
     ``prefix_slot`` (the shared prefix, no per-sequence copy).  One MFMA
     kernel (csrc/prefill_attn.hip); ``nsplit`` > 1 splits every query tile's
     keys over that many blocks plus a merge kernel (0 = :func:`prefill_splits`).
-    Returns [T, Hq, D] bf16."""
+    Returns [T, Hq, D] bf16.
+    ``kv_scale`` (k_scale, v_scale uint8 [S, Hkv, MAXS]): per-row scaled fp8 caches."""
     T, Hq, D = q.shape
     S, Hkv, MAXS, Dk = k_cache.shape
     _req(q, torch.bfloat16, "prefill_attention.q")
     kv8 = _req_kv(k_cache, v_cache, "prefill_attention")
+    kv_scale = _req_kv_scale(kv_scale, k_cache, "prefill_attention")
     if Dk != D or v_cache.shape != k_cache.shape or not prefill_supported(Hq, Hkv, D):
         raise HipOpsError(f"prefill_attention: unsupported shape q={tuple(q.shape)} kv={tuple(k_cache.shape)}")
     slot, start, prefix_len = int(slot), int(start), int(prefix_len)
@@ -443,6 +516,15 @@ def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     if nsplit > 1:
         part_o = torch.empty(nsplit * T * Hq * D, dtype=torch.float32, device=q.device)
         part_ml = torch.empty(nsplit * T * Hq * 2, dtype=torch.float32, device=q.device)
+    if kv_scale is not None:
+        ks, vs = kv_scale
+        pks, pvs = (ks[int(prefix_slot)], vs[int(prefix_slot)]) if prefix_len else (None, None)
+        _check(lib().dmcp_prefill_attention_scaled(_ptr(q), _ptr(k_cache[slot]), _ptr(v_cache[slot]), _ptr(pk),
+                                                   _ptr(pv), _ptr(out), _ptr(part_o), _ptr(part_ml), T, start,
+                                                   prefix_len, Hq, Hkv, D, MAXS, float(scale), int(variant),
+                                                   int(nsplit), _stream(), _ptr(ks[slot]), _ptr(vs[slot]), _ptr(pks),
+                                                   _ptr(pvs)), "dmcp_prefill_attention_scaled")
+        return out
     _check(lib().dmcp_prefill_attention(_ptr(q), _ptr(k_cache[slot]), _ptr(v_cache[slot]), _ptr(pk), _ptr(pv),
                                         _ptr(out), _ptr(part_o), _ptr(part_ml), T, start, prefix_len, Hq, Hkv, D,
                                         MAXS, float(scale), int(variant), int(nsplit), kv8, _stream()),
@@ -494,17 +576,19 @@ def _varlen_meta(key: tuple, device) -> tuple:
 
 def prefill_attention_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, offsets, slots, starts,
                              prefix_slot: Optional[int] = None, prefix_lens=None, scale: float = 1.0,
-                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                             out: Optional[torch.Tensor] = None, kv_scale: Optional[tuple] = None) -> torch.Tensor:
     """Packed multi-sequence prefill attention in ONE launch
     (csrc/prefill_attn.hip::prefill_varlen_kernel): q [Ttot, Hq, D], sequence
     i = rows [offsets[i], offsets[i+1]) at positions [starts[i], ...) of
     ``slots[i]``, its first ``prefix_lens[i]`` keys read in place from
     ``prefix_slot``.  Work items (sequence, 128-column tile) are ordered by
-    descending key count on the host.  Returns [Ttot, Hq, D] bf16."""
+    descending key count on the host.  Returns [Ttot, Hq, D] bf16.
+    ``kv_scale`` (k_scale, v_scale uint8 [S, Hkv, MAXS]): per-row scaled fp8 caches."""
     Ttot, Hq, D = q.shape
     S, Hkv, MAXS, Dk = k_cache.shape
     _req(q, torch.bfloat16, "prefill_attention_varlen.q")
     kv8 = _req_kv(k_cache, v_cache, "prefill_attention_varlen")
+    kv_scale = _req_kv_scale(kv_scale, k_cache, "prefill_attention_varlen")
     if Dk != D or v_cache.shape != k_cache.shape or not prefill_supported(Hq, Hkv, D):
         raise HipOpsError(f"prefill_attention_varlen: unsupported shape q={tuple(q.shape)} kv={tuple(k_cache.shape)}")
     n = len(slots)
@@ -530,6 +614,14 @@ def prefill_attention_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: to
         pk, pv = k_cache[int(prefix_slot)], v_cache[int(prefix_slot)]
     else:
         pk = pv = None
+    if kv_scale is not None:
+        ks, vs = kv_scale
+        pks, pvs = (ks[int(prefix_slot)], vs[int(prefix_slot)]) if any(plens) else (None, None)
+        _check(lib().dmcp_prefill_varlen_scaled(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(pk), _ptr(pv), _ptr(out),
+                                                _ptr(it_t), _ptr(seq_t), n_items, Hq, Hkv, D, MAXS, Hkv * MAXS * D,
+                                                float(scale), _stream(), _ptr(ks), _ptr(vs), _ptr(pks), _ptr(pvs)),
+               "dmcp_prefill_varlen_scaled")
+        return out
     _check(lib().dmcp_prefill_varlen(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(pk), _ptr(pv), _ptr(out),
                                      _ptr(it_t), _ptr(seq_t), n_items, Hq, Hkv, D, MAXS, Hkv * MAXS * D,
                                      float(scale), kv8, _stream()), "dmcp_prefill_varlen")
@@ -899,11 +991,15 @@ def pgemm_set_group(g: int) -> int:
     return int(lib().dmcp_pgemm_set_group(int(g)))
 
 
-def kv_fork(k_cache: torch.Tensor, v_cache: torch.Tensor, src: int, dsts, start: int, end: int) -> None:
+def kv_fork(k_cache: torch.Tensor, v_cache: torch.Tensor, src: int, dsts, start: int, end: int,
+            kv_scale: Optional[tuple] = None) -> None:
     """Slot ``src``'s K/V at positions [start, end) of every layer into each
     slot of ``dsts`` (<= 32): one launch for both caches
-    ([layers, slots, Hkv, max_seq, D] bf16, or e4m3 bytes)."""
+    ([layers, slots, Hkv, max_seq, D] bf16, or e4m3 bytes).  ``kv_scale``
+    (k_scale, v_scale uint8 [layers, slots, Hkv, max_seq]): the rows' exponent
+    bytes move with them (a second launch)."""
     _req_kv(k_cache, v_cache, "kv_fork")
+    kv_scale = _req_kv_scale(kv_scale, k_cache, "kv_fork")
     if k_cache.dim() != 5 or not k_cache.is_contiguous() or not v_cache.is_contiguous():
         raise HipOpsError("kv_fork: caches must be contiguous [layers, slots, Hkv, max_seq, D]")
     L, S, H, T, D = k_cache.shape
@@ -912,9 +1008,14 @@ def kv_fork(k_cache: torch.Tensor, v_cache: torch.Tensor, src: int, dsts, start:
         return
     if len(dl) > 32:
         for i in range(0, len(dl), 32):
-            kv_fork(k_cache, v_cache, src, dl[i:i + 32], start, end)
+            kv_fork(k_cache, v_cache, src, dl[i:i + 32], start, end, kv_scale)
         return
     arr = (ctypes.c_int32 * len(dl))(*dl)
+    if kv_scale is not None:
+        _check(lib().dmcp_kv_fork_scaled(_ptr(k_cache), _ptr(v_cache), L, S, H, T, D, int(src),
+                                         ctypes.cast(arr, ctypes.c_void_p), len(dl), int(start), int(end), _stream(),
+                                         _ptr(kv_scale[0]), _ptr(kv_scale[1])), "dmcp_kv_fork_scaled")
+        return
     _check(lib().dmcp_kv_fork(_ptr(k_cache), _ptr(v_cache), L, S, H, T, D * k_cache.element_size(), int(src),
                               ctypes.cast(arr, ctypes.c_void_p),
                               len(dl), int(start), int(end), _stream()), "dmcp_kv_fork")
@@ -1014,16 +1115,24 @@ def _fused(epi: str, wk: int, x, w, out, M, K, N, eps=0.0, inter=0, pos=None, sl
 def fused_rope_kv(x: torch.Tensor, w: torch.Tensor, eps: float, pos: torch.Tensor, slot: torch.Tensor,
                   cos_sin: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int,
                   q_out: Optional[torch.Tensor] = None, wk: int = 8,
-                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None) -> torch.Tensor:
+                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None,
+                  kv_scale: Optional[tuple] = None) -> torch.Tensor:
     """q = RoPE(rms(x) . w[:Hq*D]^T); RoPE(k) and v appended to the KV cache at
     (slot[m], :, pos[m]) -- the RMSNorm weight must be folded into ``w``.
     x [M, K]; w [(Hq + 2 Hkv) D, K]; caches [S, Hkv, MAXS, D]; ``bias`` [N]
     bf16 is added to the normalised fp32 product before RoPE.  Returns q [M, Hq, D].
     ``qk_norm`` is the CPU reference's only: this kernel's tile holds 32 of a
-    head's columns, so a QK-norm model runs fused_linear_norm + rope_kv."""
+    head's columns, so a QK-norm model runs fused_linear_norm + rope_kv.
+    ``kv_scale`` is refused: a block holds 32 of a head's columns, so the
+    per-row scaled (fp8s) cache has no writer here -- its small steps run
+    wgemm_rope_kv, or fused_linear_norm + rope_kv."""
     if qk_norm is not None:
         raise HipOpsError("fused_rope_kv: the kernel takes no qk_norm (a block holds 32 of a head's columns); "
                           "use fused_linear_norm followed by rope_kv(qk_norm=...)")
+    if kv_scale is not None:
+        raise HipOpsError("fused_rope_kv: the kernel has no per-row scaled (fp8s) cache writer (a block holds 32 of "
+                          "a head's columns); use wgemm_rope_kv(kv_scale=...) or fused_linear_norm + "
+                          "rope_kv(kv_scale=...)")
     M, K, N = _fused_xw(x, w, "fused_rope_kv")
     _req_bias(bias, N, "fused_rope_kv")
     S, Hkv, MAXS, D = k_cache.shape
@@ -1295,14 +1404,16 @@ def wgemm_resid_norm(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor, n
 def wgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
                   k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, workspace: torch.Tensor,
                   q_out: Optional[torch.Tensor] = None, splits: int = 0,
-                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None) -> torch.Tensor:
+                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None,
+                  kv_scale: Optional[tuple] = None) -> torch.Tensor:
     """rope_kv(F.linear(x, w, bias), ...) as one split-K GEMM + one reduction per
     row (the bias on the fp32 sum, RoPE, the q write and the K/V-cache append).
     x [M, K] (M <= WGEMM_MAX_ROWS); returns q [M, Hq, D].  ``qk_norm``
     (q_weight [D], k_weight [D], eps): per-head RMSNorm of q and k between the
-    bias and the rotation, in the same reduction."""
+    bias and the rotation, in the same reduction.
+    ``kv_scale`` (k_scale, v_scale): the reduction appends in the per-row scaled fp8 format."""
     return _rope_kv(_WGEMM, (x, w), pos, slot, cos_sin, k_cache, v_cache, n_q_heads, workspace, "wgemm_rope_kv",
-                    q_out, splits, bias, qk_norm)
+                    q_out, splits, bias, qk_norm, kv_scale)
 
 
 def wgemm_workspace(rows: int, n_max: int, device) -> torch.Tensor:
@@ -1651,11 +1762,13 @@ def tgemm_resid_norm(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor, n
 def tgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
                   k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, workspace: torch.Tensor,
                   q_out: Optional[torch.Tensor] = None, splits: int = 0,
-                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None) -> torch.Tensor:
+                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None,
+                  kv_scale: Optional[tuple] = None) -> torch.Tensor:
     """rope_kv(F.linear(x, w, bias), ...) as the large-tile split-K GEMM + the
-    fused bias / RoPE / q write / KV-append reduction; returns q [M, Hq, D]."""
+    fused bias / RoPE / q write / KV-append reduction; returns q [M, Hq, D].
+    ``kv_scale`` (k_scale, v_scale): the reduction appends in the per-row scaled fp8 format."""
     return _rope_kv(_TGEMM, (x, w), pos, slot, cos_sin, k_cache, v_cache, n_q_heads, workspace, "tgemm_rope_kv",
-                    q_out, splits, bias, qk_norm)
+                    q_out, splits, bias, qk_norm, kv_scale)
 
 
 def tgemm_lm_head_argmax(x: torch.Tensor, w: torch.Tensor, masks: torch.Tensor, mask_idx: torch.Tensor,
@@ -1843,7 +1956,7 @@ def _rope_kv_args(name: str, M: int, N: int, pos: torch.Tensor, slot: torch.Tens
 def _rope_kv(fam: _Family, ops: tuple, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
              k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, workspace: torch.Tensor, name: str,
              q_out: Optional[torch.Tensor] = None, splits: int = 0, bias: Optional[torch.Tensor] = None,
-             qk_norm: Optional[tuple] = None) -> torch.Tensor:
+             qk_norm: Optional[tuple] = None, kv_scale: Optional[tuple] = None) -> torch.Tensor:
     """The partials GEMM of the QKV projection, then the reduction that adds
     the bias, (``qk_norm``) normalises the q / k heads, rotates them, writes q
     and appends k / v to the caches."""
@@ -1852,7 +1965,16 @@ def _rope_kv(fam: _Family, ops: tuple, pos: torch.Tensor, slot: torch.Tensor, co
     q_out, kv8 = _rope_kv_args(name, M, N, pos, slot, cos_sin, k_cache, v_cache, n_q_heads, q_out)
     slots, Hkv, max_seq, D = k_cache.shape
     qk_norm = _req_qk_norm(qk_norm, D, name)
+    kv_scale = _req_kv_scale(kv_scale, k_cache, name)
     fam.launch(ops, workspace, *dims)
+    if kv_scale is not None:
+        qw, kw, neps = qk_norm if qk_norm is not None else (None, None, 0.0)
+        _check(lib().dmcp_reduce_rope_kv_scaled(_ptr(workspace), S, _ptr(pos), _ptr(slot), _ptr(cos_sin), _ptr(q_out),
+                                                _ptr(k_cache), _ptr(v_cache), M, n_q_heads, Hkv, D, max_seq,
+                                                cos_sin.shape[0], slots, _stream(), _ptr(bias), _ptr(qw), _ptr(kw),
+                                                neps, _ptr(kv_scale[0]), _ptr(kv_scale[1])),
+               "dmcp_reduce_rope_kv_scaled")
+        return q_out
     if qk_norm is not None:
         qw, kw, neps = qk_norm
         _check(lib().dmcp_reduce_rope_kv_norm(_ptr(workspace), S, _ptr(pos), _ptr(slot), _ptr(cos_sin), _ptr(q_out),

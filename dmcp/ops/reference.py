@@ -47,6 +47,74 @@ def kv_encode(x: torch.Tensor, cache_dtype: torch.dtype) -> torch.Tensor:
     return x.to(cache_dtype)
 
 
+# ---- per-row scaled FP8 KV cache (kv_dtype "fp8s"): the e4m3 bytes of a
+# cached row (one kv head's D values at one position) plus one exponent byte,
+# kept in tables beside the caches: k_scale / v_scale uint8 [S, Hkv, MAXS] for
+# caches [S, Hkv, MAXS, D].  With amax the largest |x| of the row's bf16 values:
+#   e     = the smallest exponent with amax / 2^e <= 448, 0 for an all-zero row
+#           (the MX rule of :func:`mx_quant`; csrc/dmcp_common.hpp mx_exp)
+#   byte  = e + 127
+#   bytes = e4m3(x * 2^-e)        (the scaling is exact; saturating convert)
+# and a reader decodes e4m3 * 2^(byte - 127) for ANY byte 0 .. 254, not only the
+# minimal one (255 is E8M0's NaN: 2^128 is no fp32 value, no writer produces it).
+# The ops below take the tables as ``kv_scale=(k_scale, v_scale)``; None is the
+# unit-scale format.
+KV_FORMATS = ("bf16", "fp8", "fp8s")
+
+
+def kv_row_exp(amax: torch.Tensor) -> torch.Tensor:
+    """The row exponent e (int32) of rows whose largest magnitude is ``amax``."""
+    af = amax.float()
+    _, e = torch.frexp(af * torch.tensor(1.0 / FP8_MAX, dtype=torch.float32, device=af.device))
+    return torch.where(af > 0, e, torch.zeros_like(e)).clamp(-127, 127).to(torch.int32)
+
+
+def _pow2(e: torch.Tensor) -> torch.Tensor:
+    """2^e (fp64, exact) of integer exponents in [-1022, 1023], built from the
+    bits: ``torch.ldexp`` multiplies by a computed ``pow`` that is one ulp short
+    on some devices, which moves values that sit on an e4m3 rounding tie."""
+    return ((e.to(torch.int64) + 1023) << 52).view(torch.float64)
+
+
+def kv_encode_scaled(x: torch.Tensor) -> tuple:
+    """x [..., D] -> (e4m3 bytes uint8 [..., D], exponent bytes uint8 [...])."""
+    xf = x.float()
+    e = kv_row_exp(xf.abs().amax(-1))
+    q = (xf.double() * _pow2(-e)[..., None]).float()
+    return (q.clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn).view(torch.uint8),
+            (e + 127).to(torch.uint8))
+
+
+def kv_decode_scaled(q: torch.Tensor, s: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """The values [..., D] (``dtype``: fp32 or fp64) of e4m3 bytes ``q`` under
+    the exponent bytes ``s`` [...] -- any byte, minimal or not."""
+    v = q.view(torch.float8_e4m3fn).to(torch.float64)
+    return (v * _pow2(s.to(torch.int32) - 127)[..., None]).to(dtype)
+
+
+def _kv_rows(cache: torch.Tensor, scale: Optional[torch.Tensor], idx) -> torch.Tensor:
+    """``cache[idx]`` as floats (:func:`kv_float`), decoded with ``scale[idx]``
+    where the cache is a scaled one."""
+    if scale is None:
+        return kv_float(cache[idx])
+    return kv_decode_scaled(cache[idx], scale[idx])
+
+
+def _kv_scale_pair(kv_scale, k_cache: torch.Tensor, name: str) -> tuple:
+    """(k_scale, v_scale) validated against the caches, (None, None) for None."""
+    if kv_scale is None:
+        return None, None
+    if not isinstance(kv_scale, (tuple, list)) or len(kv_scale) != 2:
+        raise ValueError(f"{name}: kv_scale must be (k_scale, v_scale)")
+    if k_cache.dtype != torch.uint8:
+        raise ValueError(f"{name}: kv_scale needs fp8 (uint8) caches, got {k_cache.dtype}")
+    for t, which in zip(kv_scale, ("k_scale", "v_scale")):
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or tuple(t.shape) != tuple(k_cache.shape[:-1])
+                or t.device != k_cache.device):
+            raise ValueError(f"{name}.{which}: expected uint8 {tuple(k_cache.shape[:-1])} on the caches' device")
+    return kv_scale[0], kv_scale[1]
+
+
 ROPE_TYPES = ("default", "linear", "llama3")
 
 
@@ -144,10 +212,12 @@ def head_rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float) -> torch.Ten
 
 def rope_kv(qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
             k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, q_out: Optional[torch.Tensor] = None,
-            qk_norm: Optional[tuple] = None) -> torch.Tensor:
+            qk_norm: Optional[tuple] = None, kv_scale: Optional[tuple] = None) -> torch.Tensor:
     """``qk_norm`` (q_weight [D], k_weight [D], eps): per-head RMSNorm of the q
-    and k heads in fp32 between the projection and the rotation."""
+    and k heads in fp32 between the projection and the rotation.
+    ``kv_scale`` (k_scale, v_scale): append in the per-row scaled fp8 format."""
     S, Hkv, MAXS, D = k_cache.shape
+    ks, vs = _kv_scale_pair(kv_scale, k_cache, "rope_kv")
     T = qkv.shape[0]
     x = qkv.view(T, n_q_heads + 2 * Hkv, D)
     xq, xk = x[:, :n_q_heads], x[:, n_q_heads:n_q_heads + Hkv]
@@ -159,7 +229,10 @@ def rope_kv(qkv: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: t
     v = x[:, n_q_heads + Hkv:]
     for t in range(T):
         p, s = int(pos[t]), int(slot[t])
-        if 0 <= p < MAXS and 0 <= s < S:
+        if 0 <= p < MAXS and 0 <= s < S and ks is not None:
+            k_cache[s, :, p], ks[s, :, p] = kv_encode_scaled(k[t])
+            v_cache[s, :, p], vs[s, :, p] = kv_encode_scaled(v[t])
+        elif 0 <= p < MAXS and 0 <= s < S:
             k_cache[s, :, p] = kv_encode(k[t], k_cache.dtype)
             v_cache[s, :, p] = kv_encode(v[t], v_cache.dtype)
     if q_out is not None:
@@ -176,10 +249,15 @@ def _linear_f32(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]) 
 def fused_rope_kv(x: torch.Tensor, w: torch.Tensor, eps: float, pos: torch.Tensor, slot: torch.Tensor,
                   cos_sin: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int,
                   q_out: Optional[torch.Tensor] = None, wk: int = 8,
-                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None) -> torch.Tensor:
+                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None,
+                  kv_scale: Optional[tuple] = None) -> torch.Tensor:
     """rope_kv(rms(x) . w^T + bias) with the product kept in fp32 up to RoPE
     (the fused kernel rotates its accumulator); ``wk`` is the kernel's.
-    ``qk_norm`` is part of this CPU model only: the HIP kernel takes none."""
+    ``qk_norm`` is part of this CPU model only: the HIP kernel takes none.
+    ``kv_scale``: the fused kernel has no scaled writer -- a ValueError, as on the GPU."""
+    if kv_scale is not None:
+        raise ValueError("fused_rope_kv: no per-row scaled (fp8s) cache writer; use wgemm_rope_kv, or "
+                         "fused_linear_norm + rope_kv")
     xf = x.float()
     xn = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
     return rope_kv(_linear_f32(xn, w, bias), pos, slot, cos_sin, k_cache, v_cache, n_q_heads, q_out,
@@ -189,43 +267,54 @@ def fused_rope_kv(x: torch.Tensor, w: torch.Tensor, eps: float, pos: torch.Tenso
 def wgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
                   k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, workspace=None,
                   q_out: Optional[torch.Tensor] = None, splits: int = 0,
-                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None) -> torch.Tensor:
+                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None,
+                  kv_scale: Optional[tuple] = None) -> torch.Tensor:
     """rope_kv(bf16(x . w^T + bias)): the split-K reduction rounds the biased
     fp32 sum to bf16 before the QK-norm and RoPE (what F.linear + rope_kv
     compute)."""
     return rope_kv(_linear_f32(x, w, bias).to(torch.bfloat16), pos, slot, cos_sin, k_cache, v_cache, n_q_heads, q_out,
-                   qk_norm=qk_norm)
+                   qk_norm=qk_norm, kv_scale=kv_scale)
 
 
 def tgemm_rope_kv(x: torch.Tensor, w: torch.Tensor, pos: torch.Tensor, slot: torch.Tensor, cos_sin: torch.Tensor,
                   k_cache: torch.Tensor, v_cache: torch.Tensor, n_q_heads: int, workspace=None,
                   q_out: Optional[torch.Tensor] = None, splits: int = 0,
-                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None) -> torch.Tensor:
+                  bias: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None,
+                  kv_scale: Optional[tuple] = None) -> torch.Tensor:
     """The same composition as :func:`wgemm_rope_kv` (one reduction serves both)."""
     return wgemm_rope_kv(x, w, pos, slot, cos_sin, k_cache, v_cache, n_q_heads, workspace, q_out, splits, bias,
-                         qk_norm)
+                         qk_norm, kv_scale)
 
 
 class SharedPrefix(NamedTuple):
     """Keys/values shared by the rows of a decode step (cascade decoding):
     ``k`` / ``v`` [Hkv, MAXS, D] (the prefix slot of the caches),
     ``length`` int32 [1] on the device (0 = no prefix) and ``rows`` (int32
-    [B], optional: 0 = this row does not use the prefix)."""
+    [B], optional: 0 = this row does not use the prefix).  ``k_scale`` /
+    ``v_scale`` [Hkv, MAXS]: the prefix slot's exponent bytes (per-row scaled
+    caches only)."""
     k: torch.Tensor
     v: torch.Tensor
     length: torch.Tensor
     rows: Optional[torch.Tensor] = None
+    k_scale: Optional[torch.Tensor] = None
+    v_scale: Optional[torch.Tensor] = None
 
 
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slot: torch.Tensor,
                      seq_len: torch.Tensor, scale: float, workspace=None, chunk: int = 256,
                      out: Optional[torch.Tensor] = None, prefix: Optional[SharedPrefix] = None,
-                     fork: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     fork: Optional[torch.Tensor] = None, kv_scale: Optional[tuple] = None) -> torch.Tensor:
     """``fork`` [S, 2] (parent slot, end): keys below ``end`` of a row whose
     slot has a parent come from the parent's slot (a method branch reading
-    its class head's KV in place)."""
+    its class head's KV in place).  ``kv_scale`` (k_scale, v_scale): the caches
+    are per-row scaled fp8; every key is decoded with the exponent byte of the
+    slot it is read from (``prefix.k_scale`` / ``v_scale`` for the prefix)."""
     B, Hq, D = q.shape
     S, Hkv, MAXS, _ = k_cache.shape
+    ks, vs = _kv_scale_pair(kv_scale, k_cache, "decode_attention")
+    if ks is not None and prefix is not None and (prefix.k_scale is None or prefix.v_scale is None):
+        raise ValueError("decode_attention: a scaled cache's prefix needs k_scale / v_scale")
     G = Hq // Hkv
     P = int(prefix.length.reshape(-1)[0]) if prefix is not None else 0
     res = torch.zeros((B, Hq, D), dtype=kv_float(q).dtype, device=q.device)
@@ -233,16 +322,19 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
         s, L = int(slot[b]), min(int(seq_len[b]), MAXS)
         if not (0 <= s < S) or L <= 0:
             continue
-        k = kv_float(k_cache[s, :, :L])  # [Hkv, L, D]
-        v = kv_float(v_cache[s, :, :L])
+        own = (s, slice(None), slice(0, L))
+        k = _kv_rows(k_cache, ks, own)  # [Hkv, L, D]
+        v = _kv_rows(v_cache, vs, own)
         if fork is not None:
             ps, fe = int(fork[s, 0]), min(int(fork[s, 1]), L)
             if fe > 0 and 0 <= ps < S and ps != s:
-                k = torch.cat([kv_float(k_cache[ps, :, :fe]), k[:, fe:]], dim=1)
-                v = torch.cat([kv_float(v_cache[ps, :, :fe]), v[:, fe:]], dim=1)
+                par = (ps, slice(None), slice(0, fe))
+                k = torch.cat([_kv_rows(k_cache, ks, par), k[:, fe:]], dim=1)
+                v = torch.cat([_kv_rows(v_cache, vs, par), v[:, fe:]], dim=1)
         if P > 0 and (prefix.rows is None or int(prefix.rows[b]) != 0):  # the first P keys: the shared prefix
-            k = torch.cat([kv_float(prefix.k[:, :P]), k[:, P:]], dim=1)
-            v = torch.cat([kv_float(prefix.v[:, :P]), v[:, P:]], dim=1)
+            pre = (slice(None), slice(0, P))
+            k = torch.cat([_kv_rows(prefix.k, prefix.k_scale if ks is not None else None, pre), k[:, P:]], dim=1)
+            v = torch.cat([_kv_rows(prefix.v, prefix.v_scale if ks is not None else None, pre), v[:, P:]], dim=1)
         qb = kv_float(q[b]).view(Hkv, G, D)
         att = torch.einsum("hgd,hld->hgl", qb, k) * scale
         p = torch.softmax(att, dim=-1)
@@ -256,19 +348,24 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
 
 def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slot: int, start: int,
                       prefix_slot: Optional[int] = None, prefix_len: int = 0, scale: float = 1.0,
-                      out: Optional[torch.Tensor] = None, variant: int = 0, nsplit: int = 0) -> torch.Tensor:
+                      out: Optional[torch.Tensor] = None, variant: int = 0, nsplit: int = 0,
+                      kv_scale: Optional[tuple] = None) -> torch.Tensor:
     """q [T, Hq, D] at positions [start, start+T) of ``slot``; every query
     sees the keys at or before its position.  Keys [0, prefix_len) come from
-    ``prefix_slot``, the rest from ``slot``.  fp32 math, returns [T, Hq, D]."""
+    ``prefix_slot``, the rest from ``slot``.  fp32 math, returns [T, Hq, D].
+    ``kv_scale`` (k_scale, v_scale): per-row scaled fp8 caches."""
     T, Hq, D = q.shape
     Hkv = k_cache.shape[1]
     G = Hq // Hkv
     L = start + T
-    k = kv_float(k_cache[slot, :, :L])
-    v = kv_float(v_cache[slot, :, :L])
+    ks, vs = _kv_scale_pair(kv_scale, k_cache, "prefill_attention")
+    own = (slot, slice(None), slice(0, L))
+    k = _kv_rows(k_cache, ks, own)
+    v = _kv_rows(v_cache, vs, own)
     if prefix_len > 0:
-        k = torch.cat([kv_float(k_cache[prefix_slot, :, :prefix_len]), k[:, prefix_len:]], dim=1)
-        v = torch.cat([kv_float(v_cache[prefix_slot, :, :prefix_len]), v[:, prefix_len:]], dim=1)
+        pre = (prefix_slot, slice(None), slice(0, prefix_len))
+        k = torch.cat([_kv_rows(k_cache, ks, pre), k[:, prefix_len:]], dim=1)
+        v = torch.cat([_kv_rows(v_cache, vs, pre), v[:, prefix_len:]], dim=1)
     qf = kv_float(q).view(T, Hkv, G, D)
     att = torch.einsum("thgd,hld->hgtl", qf, k) * scale  # [Hkv, G, T, L]
     pos = torch.arange(start, L, device=q.device)[:, None]
@@ -282,7 +379,7 @@ def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
 
 def prefill_attention_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, offsets, slots, starts,
                              prefix_slot: Optional[int] = None, prefix_lens=None, scale: float = 1.0,
-                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                             out: Optional[torch.Tensor] = None, kv_scale: Optional[tuple] = None) -> torch.Tensor:
     """Several sequences' prefill in one packed q [Ttot, Hq, D]: sequence i
     is rows [offsets[i], offsets[i+1]) at positions [starts[i], ...) of
     ``slots[i]``, keys [0, prefix_lens[i]) read from ``prefix_slot``.
@@ -292,7 +389,7 @@ def prefill_attention_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: to
         a, b = int(offsets[i]), int(offsets[i + 1])
         P = int(prefix_lens[i]) if prefix_lens is not None else 0
         out[a:b] = prefill_attention(q[a:b], k_cache, v_cache, int(slots[i]), int(starts[i]),
-                                     prefix_slot if P else None, P, scale)
+                                     prefix_slot if P else None, P, scale, kv_scale=kv_scale)
     return out
 
 

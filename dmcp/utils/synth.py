@@ -442,7 +442,7 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
                      outliers=(7, 300, 1029, 1800), seed: int = 11, device: str = "cuda", rope_scaling=None,
                      qkv_bias: bool = False, model_type: Optional[str] = None, tie_embeddings: bool = False,
                      head_dim: Optional[int] = None, qk_norm: bool = False,
-                     chat_template: Optional[str] = None) -> str:
+                     chat_template: Optional[str] = None, k_bias_scale: float = 1.0) -> str:
     """A Llama-format checkpoint directory (``config.json``, one
     ``model.safetensors``, ``tokenizer.json``) with *trained-like* random
     weights -- no download exists here: heavy-tailed matrices (a Gaussian
@@ -456,7 +456,9 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
     ``rope_scaling``: a dict written to config.json as is.  ``qkv_bias``: q/k/v
     projection biases drawn N(0, 2^2) after every other tensor -- a Qwen2
     checkpoint's layout with values no loader can drop unnoticed, far from
-    fp8 saturation.  ``model_type="qwen2"`` writes the Qwen2 config keys;
+    fp8 saturation; ``k_bias_scale`` multiplies the drawn K bias (the same
+    draws: 1.0 writes the same tensors), so K rows can be pushed past e4m3's
+    +-448 as Qwen2.5-Coder's are.  ``model_type="qwen2"`` writes the Qwen2 config keys;
     ``tie_embeddings`` omits ``lm_head.weight``; ``head_dim`` decouples the
     head width from hidden / heads.  ``qk_norm``: per-head ``q_norm`` /
     ``k_norm`` weights [head_dim] drawn like the other norm weights (1 +- 0.25)
@@ -509,6 +511,8 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
             p = f"model.layers.{i}."
             for n, rows in (("q", heads * hd), ("k", kv_heads * hd), ("v", kv_heads * hd)):
                 b = 2.0 * torch.randn(rows, generator=g, device=device)
+                if n == "k" and k_bias_scale != 1.0:
+                    b = b * k_bias_scale
                 t[p + f"self_attn.{n}_proj.bias"] = b.to(torch.bfloat16).cpu()
     if qk_norm:  # drawn last: every tensor above is what a call without it writes
         for i in range(layers):

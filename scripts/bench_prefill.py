@@ -23,7 +23,7 @@ def main() -> int:
     ap.add_argument("--prefix", type=int, default=4151)
     ap.add_argument("--tokens", type=int, default=2100)
     ap.add_argument("--seqs", type=int, default=12)
-    ap.add_argument("--kv-dtype", default="fp8", choices=["bf16", "fp8"])
+    ap.add_argument("--kv-dtype", default="fp8", choices=["bf16", "fp8", "fp8s"])
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--prefill-dtype", default="bf16", choices=["auto", "bf16", "fp8"])
     a = ap.parse_args()

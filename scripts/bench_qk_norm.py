@@ -87,7 +87,7 @@ def main(argv=None) -> int:
     ap.add_argument("--ctx", type=int, default=64)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8", "fp8s"])
     a = ap.parse_args(argv)
     from dmcp.models.llm import LocalLM
     from dmcp.utils import synth

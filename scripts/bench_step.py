@@ -31,7 +31,7 @@ import torch  # noqa: E402
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--preset", default="dmcp-coder-1b")
-    ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"],
+    ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8", "fp8s"],
                     help="KV cache storage (fp8 = e4m3, half the attention bytes)")
     ap.add_argument("--decode-dtype", default="bf16", choices=["bf16", "fp8"],
                     help="decode projections: bf16 or fp8 weights x MXFP8 activations")
