@@ -324,8 +324,9 @@ class GpuWorkerPool:
                     who.info = msg
                     self._rebalance()
                 wit = msg.get("witness") or {}
-                LOG.info("GPU worker %d ready on %s (pid %s, chat template %s, KV cache %s)", who.index, who.device,
-                         msg.get("pid"), wit.get("chat_template", "n/a"), wit.get("kv_dtype", "n/a"))
+                LOG.info("GPU worker %d ready on %s (pid %s, chat template %s, KV cache %s%s)", who.index, who.device,
+                         msg.get("pid"), wit.get("chat_template", "n/a"), wit.get("kv_dtype", "n/a"),
+                         f", moe={wit['moe']}" if wit.get("moe") else "")
         if not any(w.ready and w.alive for w in self.workers):
             raise RuntimeError("no GPU worker started")
         self._initialised = True
@@ -732,6 +733,8 @@ def _witness(dev: str, model=None) -> dict:
     per-row scaled), so a checkpoint left on the saturating default shows in
     the log."""
     kv = {"kv_dtype": model.cfg.kv_dtype} if model is not None else {}
+    if model is not None and getattr(model.cfg, "n_experts", 0):  # a routed expert MLP: "<experts>x<per token>"
+        kv["moe"] = f"{model.cfg.n_experts}x{model.cfg.experts_per_tok}"
     if not dev.startswith("cuda"):
         return {"device": dev, **kv}
     try:

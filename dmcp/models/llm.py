@@ -40,9 +40,10 @@ MI355X mapping:
   (:class:`DecodeGraphs`), removing ~10 launches/layer of host overhead.
 
 Weights are random-initialised by default (no checkpoint on this host) or
-loaded from a Llama-, Qwen2- or Qwen3-format safetensors directory
-(``load_safetensors``: RoPE scaling, q/k/v biases and Qwen3's per-head q/k
-RMSNorm included; a directory
+loaded from a Llama-, Qwen2-, Qwen3- or Qwen3-MoE-format safetensors directory
+(``load_safetensors``: RoPE scaling, q/k/v biases, Qwen3's per-head q/k
+RMSNorm and Qwen3-MoE's routed expert MLP -- ``ops.moe_mlp``, csrc/moe.hip, on
+every forward path -- included; a directory
 it cannot reproduce is refused, ``check_checkpoint``).
 """
 from __future__ import annotations
@@ -106,14 +107,24 @@ class LMConfig:
     # (key, value) pairs of its rope_scaling dict (ops.reference.rope_scaling_key:
     # "linear" or "llama3"; hashable, so a config stays a dict key)
     rope_scaling: Optional[tuple] = None
+    # mixture-of-experts MLP (Qwen3-MoE): every layer's MLP is a router over
+    # n_experts SwiGLU experts of width moe_intermediate, experts_per_tok of
+    # them per token, their probabilities renormalised when norm_topk
+    # (ops.moe_mlp, csrc/moe.hip).  n_experts 0: the dense MLP of `intermediate`
+    n_experts: int = 0
+    experts_per_tok: int = 0
+    moe_intermediate: int = 0
+    norm_topk: bool = True
 
     @property
     def qkv_dim(self) -> int:
         return (self.n_heads + 2 * self.n_kv_heads) * self.head_dim
 
     def param_count(self) -> int:
+        mlp = (3 * self.intermediate * self.hidden if not self.n_experts
+               else self.n_experts * (3 * self.moe_intermediate + 1) * self.hidden)
         per_layer = (self.qkv_dim * self.hidden + self.n_heads * self.head_dim * self.hidden
-                     + 3 * self.intermediate * self.hidden + 2 * self.hidden)
+                     + mlp + 2 * self.hidden)
         return self.layers * per_layer + 2 * self.vocab_size * self.hidden + self.hidden
 
     @property
@@ -200,8 +211,36 @@ class CheckpointUnsupported(ValueError):
     (:func:`check_checkpoint` gives the reason)."""
 
 
-SUPPORTED_MODEL_TYPES = ("llama", "qwen2", "qwen3")
-SUPPORTED_ARCHITECTURES = ("LlamaForCausalLM", "Qwen2ForCausalLM", "Qwen3ForCausalLM")
+SUPPORTED_MODEL_TYPES = ("llama", "qwen2", "qwen3", "qwen3_moe")
+SUPPORTED_ARCHITECTURES = ("LlamaForCausalLM", "Qwen2ForCausalLM", "Qwen3ForCausalLM", "Qwen3MoeForCausalLM")
+MOE_ARCHITECTURE = "Qwen3MoeForCausalLM"
+_DENSE_MLP = ("mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
+_EXPERT_PROJS = ("gate_proj", "up_proj", "down_proj")
+
+
+def _moe_config(hf: dict) -> Tuple[Optional[tuple], Optional[str]]:
+    """((n_experts, experts_per_tok, moe_intermediate, norm_topk), None) of a
+    ``qwen3_moe`` config.json, or (None, reason) naming the key."""
+    ne = hf.get("num_experts", hf.get("num_local_experts"))
+    if not isinstance(ne, int) or ne <= 0:
+        return None, "model_type 'qwen3_moe' needs num_experts (or num_local_experts) in config.json"
+    k, inter = hf.get("num_experts_per_tok"), hf.get("moe_intermediate_size")
+    if not isinstance(k, int) or k <= 0:
+        return None, "config.json: num_experts_per_tok is missing or not a positive integer"
+    if not isinstance(inter, int) or inter <= 0:
+        return None, "config.json: moe_intermediate_size is missing or not a positive integer"
+    if k > ne:
+        return None, f"num_experts_per_tok {k} exceeds num_experts {ne}"
+    if hf.get("mlp_only_layers"):
+        return None, (f"mlp_only_layers {hf['mlp_only_layers']!r} is not supported (every layer's MLP must be "
+                      f"the routed one)")
+    if hf.get("decoder_sparse_step", 1) != 1:
+        return None, f"decoder_sparse_step {hf['decoder_sparse_step']!r} is not supported (only 1: every layer sparse)"
+    if not ops.moe_supported(hf["hidden_size"], inter, ne, k):
+        return None, (f"hidden_size {hf['hidden_size']} / moe_intermediate_size {inter} / num_experts {ne} / "
+                      f"num_experts_per_tok {k} are outside the routed MLP kernels' contract (hidden and "
+                      f"intermediate multiples of 64, hidden <= 8192, at most 256 experts)")
+    return (ne, k, inter, bool(hf.get("norm_topk_prob", False))), None
 _LAYER_TENSORS = ("input_layernorm.weight", "post_attention_layernorm.weight", "self_attn.q_proj.weight",
                   "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.o_proj.weight",
                   "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
@@ -246,6 +285,39 @@ def _checkpoint_tensor_shapes(path: str, suffixes: tuple) -> Dict[str, tuple]:
     return shapes
 
 
+class _LazyTensors:
+    """name -> tensor over the mapped *.safetensors files of a directory: each
+    lookup reads that tensor alone (safe_open), nothing is kept.  A context
+    manager: leaving it closes the files and drops their mappings."""
+
+    def __init__(self, files: Sequence[str]) -> None:
+        from contextlib import ExitStack
+        from safetensors import safe_open
+        self._stack = ExitStack()
+        try:
+            handles = [self._stack.enter_context(safe_open(f, framework="pt")) for f in files]
+        except BaseException:
+            self._stack.close()
+            raise
+        self._where = {k: h for h in handles for k in h.keys()}
+
+    def __enter__(self) -> "_LazyTensors":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def close(self) -> None:
+        self._where = {}
+        self._stack.close()
+
+    def __contains__(self, name: str) -> bool:
+        return name in self._where
+
+    def __getitem__(self, name: str) -> torch.Tensor:
+        return self._where[name].get_tensor(name)
+
+
 def check_checkpoint(path: str, chat_template: Optional[str] = "auto") -> Optional[str]:
     """Why the checkpoint directory ``path`` cannot be loaded as the model it
     is -- naming the config key or tensor -- or None when
@@ -286,7 +358,14 @@ def check_checkpoint(path: str, chat_template: Optional[str] = "auto") -> Option
     kvh = hf.get("num_key_value_heads", heads)
     if not isinstance(kvh, int) or kvh <= 0 or heads % kvh:
         return f"num_attention_heads {heads} is not a multiple of num_key_value_heads {kvh}"
-    qk_norm = mt == "qwen3"
+    moe = None
+    if mt == "qwen3_moe":
+        moe, why = _moe_config(hf)
+        if moe is None:
+            return why
+    if archs and (MOE_ARCHITECTURE in archs) != (moe is not None):
+        return f"architectures {archs!r} does not match model_type {mt!r}"
+    qk_norm = mt in ("qwen3", "qwen3_moe")
     head_dim = hf.get("head_dim") or hf["hidden_size"] // heads
     if qk_norm and head_dim not in QK_NORM_HEAD_DIMS:
         return f"head_dim {head_dim} is not supported with q_norm / k_norm (supported: 64, 128)"
@@ -305,7 +384,10 @@ def check_checkpoint(path: str, chat_template: Optional[str] = "auto") -> Option
     required = {"model.embed_tokens.weight", "model.norm.weight"}
     for i in range(layers):
         p = f"model.layers.{i}."
-        required.update(p + n for n in _LAYER_TENSORS)
+        required.update(p + n for n in _LAYER_TENSORS if moe is None or n not in _DENSE_MLP)
+        if moe is not None:
+            required.add(p + "mlp.gate.weight")
+            required.update(f"{p}mlp.experts.{e}.{n}.weight" for e in range(moe[0]) for n in _EXPERT_PROJS)
         consumed.update(p + n for n in _QKV_BIASES)
         if qk_norm:
             required.update(p + n for n in _QK_NORMS)
@@ -316,6 +398,8 @@ def check_checkpoint(path: str, chat_template: Optional[str] = "auto") -> Option
             continue
         if n.endswith((".o_proj.bias", ".gate_proj.bias", ".up_proj.bias", ".down_proj.bias")):
             return f"tensor {n} is not supported (only the q/k/v projections take a bias)"
+        if "shared_expert" in n:
+            return f"tensor {n} is not supported (shared experts: only Qwen3-MoE's routed experts are loaded)"
         return f"tensor {n} is not consumed by the loader (a layout other than Llama / Qwen2 / Qwen3)"
     missing = sorted(required - have)
     if missing:
@@ -335,6 +419,23 @@ def check_checkpoint(path: str, chat_template: Optional[str] = "auto") -> Option
         for n in sorted(shapes):
             if shapes[n] != (head_dim,):
                 return f"tensor {n} has shape {list(shapes[n])}, expected [{head_dim}] (head_dim)"
+    if moe is not None:
+        n_exp, _, inter, _ = moe
+        hidden = hf["hidden_size"]
+        want = {"mlp.gate.weight": ((n_exp, hidden), "num_experts, hidden_size"),
+                "gate_proj.weight": ((inter, hidden), "moe_intermediate_size, hidden_size"),
+                "up_proj.weight": ((inter, hidden), "moe_intermediate_size, hidden_size"),
+                "down_proj.weight": ((hidden, inter), "hidden_size, moe_intermediate_size")}
+        try:
+            shapes = _checkpoint_tensor_shapes(path, tuple(want))
+        except Exception as e:  # noqa: BLE001
+            return f"safetensors of {path} cannot be read ({e})"
+        for n in sorted(shapes):
+            if ".mlp." not in n:
+                continue
+            exp, keys = next(v for s, v in want.items() if n.endswith(s))
+            if shapes[n] != exp:
+                return f"tensor {n} has shape {list(shapes[n])}, expected {list(exp)} ({keys})"
     if "lm_head.weight" not in have and hf.get("tie_word_embeddings") is False:
         return "tensor lm_head.weight is missing and tie_word_embeddings is false"
     if chat_template is not None:
@@ -462,8 +563,37 @@ class LocalLM:
                              f"decode_dtype={cfg.decode_dtype!r}")
         if self.has_qk_norm and cfg.head_dim not in QK_NORM_HEAD_DIMS:
             raise ValueError(f"{cfg.name}: per-head q/k norms need head_dim 64 or 128, got {cfg.head_dim}")
+        # routed expert MLP (Qwen3-MoE): w["l{i}.router"] [E, H], w["l{i}.we_gu"] [E, 2I, H] (an expert's gate
+        # rows, then its up rows), w["l{i}.we_down"] [E, H, I], all bf16
+        self.moe = cfg.n_experts > 0
+        if self.moe:
+            if "fp8" in (cfg.prefill_dtype, cfg.decode_dtype):
+                raise ValueError(f"{cfg.name} has a routed expert MLP, which has no MXFP8 GEMM: use "
+                                 f"prefill_dtype / decode_dtype 'bf16' (LOCAL_LLM_PREFILL_DTYPE, "
+                                 f"LOCAL_LLM_DECODE_DTYPE), got prefill_dtype={cfg.prefill_dtype!r} "
+                                 f"decode_dtype={cfg.decode_dtype!r}")
+            if not 1 <= cfg.experts_per_tok <= cfg.n_experts:
+                raise ValueError(f"{cfg.name}: experts_per_tok {cfg.experts_per_tok} outside [1, n_experts "
+                                 f"{cfg.n_experts}]")
+            if torch.device(device).type == "cuda" and not ops.moe_supported(cfg.hidden, cfg.moe_intermediate,
+                                                                             cfg.n_experts, cfg.experts_per_tok):
+                raise ValueError(f"{cfg.name}: hidden {cfg.hidden} / moe_intermediate {cfg.moe_intermediate} / "
+                                 f"n_experts {cfg.n_experts} / experts_per_tok {cfg.experts_per_tok} are outside "
+                                 f"the routed MLP kernels' contract (ops.moe_supported)")
+            if "l0.router" not in self.w:
+                raise ValueError(f"{cfg.name}: n_experts {cfg.n_experts} but the weights hold no l0.router")
         self._fold_norms()
         c = cfg
+        # the routed MLP's scratch, once, like attn_ws / wgemm_ws: decode steps
+        # and prefill chunks of up to moe_rows rows (a longer prefill walks its
+        # rows in chunks: _mlp_norm)
+        self.moe_rows = self.moe_ws = None
+        if self.moe:
+            self.moe_rows = max(1, min(max(max(c.max_batch, c.max_rows), self.MOE_PREFILL_ROWS),
+                                       ops.MOE_MAX_PAIRS // c.experts_per_tok))
+            if torch.device(device).type == "cuda":
+                self.moe_ws = ops.moe_workspace(self.moe_rows, c.hidden, c.moe_intermediate, c.n_experts,
+                                                c.experts_per_tok, self.device)
         self.shared_prefix = shared_prefix
         self.num_slots = c.max_batch + (1 if shared_prefix else 0)
         self.prefix_slot = c.max_batch if shared_prefix else -1
@@ -572,7 +702,7 @@ class LocalLM:
         self.prefill_fp8 = fp8_ok and (c.prefill_dtype == "fp8"
                                        or (c.prefill_dtype == "auto" and self.device.type == "cuda"
                                            and not self.has_bias and not self.has_qk_norm
-                                           and not self.kv_scaled))
+                                           and not self.kv_scaled and not self.moe))
         self.decode_fp8 = c.decode_dtype == "fp8" and fp8_ok
         if "fp8" in (c.prefill_dtype, c.decode_dtype) and not fp8_ok:
             raise ValueError(f"fp8 GEMMs need head_dim 64, hidden % 2048 == 0 and a supported device "
@@ -600,6 +730,10 @@ class LocalLM:
     # profiles/decode_step_tgemm_ab_r5.jsonl)
     TGEMM_MLP_MIN_ROWS = 513
     TGEMM_HEAD_MIN_ROWS = 160
+    # rows of a prefill per routed-MLP launch: bounds the workspace (at the
+    # Qwen3-30B-A3B geometry 4,096 rows x 8 experts hold 50 MB of bf16 act and
+    # 268 MB of fp32 down rows) while an expert still sees ~256 rows per launch
+    MOE_PREFILL_ROWS = 4096
 
     def _check_kv_fits(self, kv_shape) -> None:
         """The KV slab is the largest allocation of the service (tens of GB at
@@ -641,6 +775,11 @@ class LocalLM:
             w[f"l{i}.ln2"] = ones(c.hidden)
             w[f"l{i}.wqkv"] = rnd(c.qkv_dim, c.hidden)
             w[f"l{i}.wo"] = rnd(c.hidden, c.n_heads * c.head_dim, std=out_std)
+            if c.n_experts:
+                w[f"l{i}.router"] = rnd(c.n_experts, c.hidden)
+                w[f"l{i}.we_gu"] = rnd(c.n_experts, 2 * c.moe_intermediate, c.hidden)
+                w[f"l{i}.we_down"] = rnd(c.n_experts, c.hidden, c.moe_intermediate, std=out_std)
+                continue
             w[f"l{i}.wgu"] = rnd(2 * c.intermediate, c.hidden)
             w[f"l{i}.wdown"] = rnd(c.hidden, c.intermediate, std=out_std)
         return w
@@ -655,7 +794,9 @@ class LocalLM:
         c = self.cfg
         pairs = [("norm_f", "lm_head")]
         for i in range(c.layers):
-            pairs += [(f"l{i}.ln1", f"l{i}.wqkv"), (f"l{i}.ln2", f"l{i}.wgu")]
+            pairs += [(f"l{i}.ln1", f"l{i}.wqkv")]
+            if not c.n_experts:  # a routed MLP keeps ln2: the router and every expert read the normalised row
+                pairs += [(f"l{i}.ln2", f"l{i}.wgu")]
         if not hasattr(self, "norm_g"):
             # the checkpoint's own norm weights: the MXFP8 paths normalise
             # with them BEFORE quantising (a folded weight leaves a trained
@@ -707,38 +848,62 @@ class LocalLM:
                        head_dim=hf.get("head_dim") or hf["hidden_size"] // heads,
                        intermediate=hf["intermediate_size"], rope_theta=theta,
                        eps=hf.get("rms_norm_eps", 1e-5), rope_scaling=scaling)
+        moe = _moe_config(hf)[0] if hf.get("model_type") == "qwen3_moe" else None
+        if moe is not None:
+            cfg = replace(cfg, n_experts=moe[0], experts_per_tok=moe[1], moe_intermediate=moe[2], norm_topk=moe[3])
         cfg = replace(cfg, **cfg_overrides)
         if cfg.prefill_dtype == "auto" and not MXFP8_CHECKPOINT_OK:
             # a real checkpoint keeps bf16 prefill GEMMs unless fp8 is asked
             # for by name: the MXFP8 prefill fails MXFP8_CHECKPOINT_GATE on
             # trained-like weights (docs/PARITY.md)
             cfg = replace(cfg, prefill_dtype="bf16")
-        raw: Dict[str, torch.Tensor] = {}
-        for fn in sorted(os.listdir(path)):
-            if fn.endswith(".safetensors"):
-                raw.update(load_file(os.path.join(path, fn), device="cpu"))
-        dev = torch.device(device)
+        files = [os.path.join(path, fn) for fn in sorted(os.listdir(path)) if fn.endswith(".safetensors")]
+        if moe is not None:
+            # 58 GB of experts at the 30B-A3B geometry: tensors are read one at
+            # a time from the mapped files, never as a second host copy
+            raw = _LazyTensors(files)
+        else:
+            raw = {}
+            for fn in files:
+                raw.update(load_file(fn, device="cpu"))
+        try:
+            dev = torch.device(device)
 
-        def g(k):
-            return raw[k].to(dtype=torch.bfloat16, device=dev).contiguous()
+            def g(k):
+                return raw[k].to(dtype=torch.bfloat16, device=dev).contiguous()
 
-        w = {"embed": g("model.embed_tokens.weight"), "norm_f": g("model.norm.weight"),
-             "lm_head": g("lm_head.weight") if "lm_head.weight" in raw else g("model.embed_tokens.weight")}
-        for i in range(cfg.layers):
-            p = f"model.layers.{i}."
-            w[f"l{i}.ln1"] = g(p + "input_layernorm.weight")
-            w[f"l{i}.ln2"] = g(p + "post_attention_layernorm.weight")
-            w[f"l{i}.wqkv"] = torch.cat([g(p + "self_attn.q_proj.weight"), g(p + "self_attn.k_proj.weight"),
-                                         g(p + "self_attn.v_proj.weight")], 0).contiguous()
-            if p + "self_attn.q_proj.bias" in raw:  # Qwen2: q/k/v biases, stacked like wqkv
-                w[f"l{i}.bqkv"] = torch.cat([g(p + "self_attn.q_proj.bias"), g(p + "self_attn.k_proj.bias"),
-                                             g(p + "self_attn.v_proj.bias")], 0).contiguous()
-            if hf.get("model_type") == "qwen3":  # per-head q / k RMSNorm weights [head_dim]
-                w[f"l{i}.qnorm"] = g(p + "self_attn.q_norm.weight")
-                w[f"l{i}.knorm"] = g(p + "self_attn.k_norm.weight")
-            w[f"l{i}.wo"] = g(p + "self_attn.o_proj.weight")
-            w[f"l{i}.wgu"] = torch.cat([g(p + "mlp.gate_proj.weight"), g(p + "mlp.up_proj.weight")], 0).contiguous()
-            w[f"l{i}.wdown"] = g(p + "mlp.down_proj.weight")
+            w = {"embed": g("model.embed_tokens.weight"), "norm_f": g("model.norm.weight"),
+                 "lm_head": g("lm_head.weight") if "lm_head.weight" in raw else g("model.embed_tokens.weight")}
+            for i in range(cfg.layers):
+                p = f"model.layers.{i}."
+                w[f"l{i}.ln1"] = g(p + "input_layernorm.weight")
+                w[f"l{i}.ln2"] = g(p + "post_attention_layernorm.weight")
+                w[f"l{i}.wqkv"] = torch.cat([g(p + "self_attn.q_proj.weight"), g(p + "self_attn.k_proj.weight"),
+                                             g(p + "self_attn.v_proj.weight")], 0).contiguous()
+                if p + "self_attn.q_proj.bias" in raw:  # Qwen2: q/k/v biases, stacked like wqkv
+                    w[f"l{i}.bqkv"] = torch.cat([g(p + "self_attn.q_proj.bias"), g(p + "self_attn.k_proj.bias"),
+                                                 g(p + "self_attn.v_proj.bias")], 0).contiguous()
+                if hf.get("model_type") in ("qwen3", "qwen3_moe"):  # per-head q / k RMSNorm weights [head_dim]
+                    w[f"l{i}.qnorm"] = g(p + "self_attn.q_norm.weight")
+                    w[f"l{i}.knorm"] = g(p + "self_attn.k_norm.weight")
+                w[f"l{i}.wo"] = g(p + "self_attn.o_proj.weight")
+                if moe is not None:
+                    E, _, inter, _ = moe
+                    w[f"l{i}.router"] = g(p + "mlp.gate.weight")
+                    gu = torch.empty((E, 2 * inter, cfg.hidden), dtype=torch.bfloat16, device=dev)
+                    down = torch.empty((E, cfg.hidden, inter), dtype=torch.bfloat16, device=dev)
+                    for e in range(E):  # straight into the stacked device tensors, one expert at a time
+                        q = f"{p}mlp.experts.{e}."
+                        gu[e, :inter].copy_(raw[q + "gate_proj.weight"])
+                        gu[e, inter:].copy_(raw[q + "up_proj.weight"])
+                        down[e].copy_(raw[q + "down_proj.weight"])
+                    w[f"l{i}.we_gu"], w[f"l{i}.we_down"] = gu, down
+                    continue
+                w[f"l{i}.wgu"] = torch.cat([g(p + "mlp.gate_proj.weight"), g(p + "mlp.up_proj.weight")], 0).contiguous()
+                w[f"l{i}.wdown"] = g(p + "mlp.down_proj.weight")
+        finally:
+            if moe is not None:
+                raw.close()  # the mapped files, now rather than at garbage collection
         m = cls(cfg, device, weights=w)
         m.checkpoint = path
         return m
@@ -760,6 +925,30 @@ class LocalLM:
     def _mlp(self, i: int, h: torch.Tensor) -> torch.Tensor:
         gu = F.linear(h, self.w[f"l{i}.wgu"])
         return F.linear(ops.silu_mul(gu), self.w[f"l{i}.wdown"])
+
+    def _moe(self, i: int, h: torch.Tensor, resid: torch.Tensor, nxt: Optional[torch.Tensor]) -> torch.Tensor:
+        """Layer i's routed expert MLP of the normalised rows ``h``, added
+        into ``resid`` in place; with ``nxt`` the rows normalised by it are
+        returned (the add_rmsnorm that follows a dense MLP, fused into the
+        combine).  More rows than the workspace holds go in chunks."""
+        c = self.cfg
+        args = (self.w[f"l{i}.router"], self.w[f"l{i}.we_gu"], self.w[f"l{i}.we_down"], c.experts_per_tok,
+                c.norm_topk)
+        T = h.shape[0]
+        if T <= self.moe_rows:
+            return ops.moe_mlp(h, *args, residual=resid, norm_w=nxt, eps=c.eps, workspace=self.moe_ws)
+        out = torch.empty_like(h) if nxt is not None else None
+        for a in range(0, T, self.moe_rows):
+            b = min(T, a + self.moe_rows)
+            ops.moe_mlp(h[a:b], *args, residual=resid[a:b], norm_w=nxt, eps=c.eps, workspace=self.moe_ws,
+                        out=None if out is None else out[a:b])
+        return resid if out is None else out
+
+    def _mlp_norm(self, i: int, h: torch.Tensor, resid: torch.Tensor, nxt: torch.Tensor) -> torch.Tensor:
+        """Layer i's MLP (dense or routed) + residual + the next RMSNorm."""
+        if self.moe:
+            return self._moe(i, h, resid, nxt)
+        return ops.add_rmsnorm(self._mlp(i, h), nxt, self.cfg.eps, residual=resid)
 
     @torch.inference_mode()
     def forward_tokens(self, tokens: torch.Tensor, slot: int, start_pos: int) -> torch.Tensor:
@@ -805,9 +994,8 @@ class LocalLM:
                     att = _extend_attention(qh, k, v, start_pos, self.scale)
                 o = F.linear(att[0].transpose(0, 1).reshape(T, c.n_heads * c.head_dim), self.w[f"l{i}.wo"])
             h = ops.add_rmsnorm(o, self.w[f"l{i}.ln2"], c.eps, residual=resid)
-            m = self._mlp(i, h)
             nxt = self.w[f"l{i + 1}.ln1"] if i + 1 < c.layers else self.w["norm_f"]
-            h = ops.add_rmsnorm(m, nxt, c.eps, residual=resid)
+            h = self._mlp_norm(i, h, resid, nxt)
         return F.linear(h[-1:], self.w["lm_head"])[0]
 
     @torch.inference_mode()
@@ -882,9 +1070,8 @@ class LocalLM:
                                                kv_scale=kvs)
             o = F.linear(att.view(Ttot, c.n_heads * c.head_dim), self.w[f"l{i}.wo"])
             h = ops.add_rmsnorm(o, self.w[f"l{i}.ln2"], c.eps, residual=resid)
-            m = self._mlp(i, h)
             nxt = self.w[f"l{i + 1}.ln1"] if i + 1 < c.layers else self.w["norm_f"]
-            h = ops.add_rmsnorm(m, nxt, c.eps, residual=resid)
+            h = self._mlp_norm(i, h, resid, nxt)
         return F.linear(h.index_select(0, last), self.w["lm_head"])
 
     def _head(self, h: torch.Tensor) -> torch.Tensor:
@@ -987,7 +1174,9 @@ class LocalLM:
                 h = ops.wgemm_resid_norm(att, self.w[f"l{i}.wo"], resid, self.w[f"l{i}.ln2"], c.eps, self.wgemm_ws)
             else:
                 h = ops.add_rmsnorm(F.linear(att, self.w[f"l{i}.wo"]), self.w[f"l{i}.ln2"], c.eps, residual=resid)
-            if mlp_t:
+            if self.moe:
+                h = self._moe(i, h, resid, nxt)
+            elif mlp_t:
                 act = ops.tgemm_swiglu(h, self.w[f"l{i}.wgu"])
                 h = ops.tgemm_resid_norm(act, self.w[f"l{i}.wdown"], resid, nxt, c.eps, self.tg_ws)
             elif wide:
@@ -1083,6 +1272,11 @@ class LocalLM:
                                        fork=self.fork_tab,
                                        prefix=self._prefix(i, prefix_rows), splits=splits, kv_scale=kvs)
             ops.fused_resid(att.view(B, c.n_heads * c.head_dim), self.w[f"l{i}.wo"], r)
+            if self.moe:
+                # the norm fused_swiglu folds into its prologue, explicit: the
+                # router and every chosen expert read the same normalised row
+                self._moe(i, ops.add_rmsnorm(r, self.w[f"l{i}.ln2"], c.eps), r, None)
+                continue
             act = ops.fused_swiglu(r, self.w[f"l{i}.wgu"], c.eps)
             ops.fused_resid(act, self.w[f"l{i}.wdown"], r)
         return ops.fused_linear_norm(r, self.w["lm_head"], c.eps)
@@ -1380,6 +1574,10 @@ class LocalLM:
             o = torch.einsum("hts,shd->thd", torch.softmax(att, -1), v).reshape(T, -1)
             x = x + o @ w[f"l{i}.wo"].t()
             h = rms(x, w[f"l{i}.ln2"])
+            if self.moe:
+                x = x + ops.reference.moe_mlp_math(h, w[f"l{i}.router"], w[f"l{i}.we_gu"], w[f"l{i}.we_down"],
+                                                   c.experts_per_tok, c.norm_topk)
+                continue
             gu = h @ w[f"l{i}.wgu"].t()
             g_, u_ = gu[:, :c.intermediate], gu[:, c.intermediate:]
             x = x + (F.silu(g_) * u_) @ w[f"l{i}.wdown"].t()

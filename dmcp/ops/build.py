@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 SRCS = [os.path.join(CSRC, "dmcp_kernels.hip"), os.path.join(CSRC, "fused_gemm.hip"),
         os.path.join(CSRC, "prefill_attn.hip"), os.path.join(CSRC, "wgemm.hip"), os.path.join(CSRC, "pgemm.hip"),
         os.path.join(CSRC, "tgemm.hip"), os.path.join(CSRC, "splitk_reduce.hip"),
-        os.path.join(CSRC, "truncate.hip")]
+        os.path.join(CSRC, "truncate.hip"), os.path.join(CSRC, "moe.hip")]
 HEADERS = [os.path.join(CSRC, "dmcp_common.hpp")]
 SRC = SRCS[0]  # kept for callers that name the main source
 TARGET = os.path.join(HERE, "_hipops.so")

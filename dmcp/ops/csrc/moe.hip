@@ -1,0 +1,476 @@
+// Routed expert MLP (Qwen3-MoE sparse block) for gfx950 / MI355X:
+//
+//   ids, p = top-k of softmax(h . Wr^T)            (fp32, ties to the lower id)
+//   y[t]   = sum_j p[t, j] * down_e(silu(gate_e(h[t])) * up_e(h[t])),  e = ids[t, j]
+//
+// bf16 operands, fp32 accumulation on v_mfma_f32_16x16x32_bf16.  Six launches,
+// every grid sized by host-known upper bounds, so the whole op is capturable
+// in a hipGraph although the routing is data dependent:
+//
+//   1. route    one wave per row: E router dot products (fp32), softmax, k
+//               rounds of a wave arg-max (value, then lower id), optional
+//               renormalisation -> ids / p [T * k]
+//   2. count    one wave per expert scans ids -> cnt [E]
+//   3. scatter  one wave per expert: its offset (sum of the counts before
+//               it), its pairs in ascending pair order (ballot + popcount: a
+//               stable counting sort without atomics) -> perm, and its rows
+//               of the tile table (expert, first pair, rows); the last wave
+//               writes the tile count
+//   4. gate/up  grid (I / 64, ceil(T k / MT) + E): a block owns one row tile
+//               and 64 gate + 64 up columns; X rows are gathered through perm
+//               into a double-buffered LDS image, weight fragments go from
+//               global memory straight to the MFMA A operand (each weight
+//               element is used once per block); SwiGLU in the epilogue,
+//               act [T k, I] bf16 in grouped order
+//   5. down     the same kernel body over act and w_down (128 columns per
+//               block), y [T k, H] fp32, one row per pair at the PAIR's index
+//               t * k + j, so the combine reads k consecutive rows
+//   6. combine  one block per row: m = bf16(sum_j p_j * y_j) in rank order,
+//               then exactly add_rmsnorm_kernel's arithmetic (residual add,
+//               bf16 residual stream, RMSNorm)
+//
+// Blocks past the live tile count (a device value) exit at once.  No atomics
+// of any kind: every output element has one writer and a fixed summation
+// order, so equal inputs give equal bits.
+#include "dmcp_common.hpp"
+
+namespace {
+
+constexpr int kMaxExperts = 256;
+constexpr int kEPL = kMaxExperts / kWave;  // expert slots per lane of the routing wave
+
+// ---------------------------------------------------------------- 1. route
+__global__ __launch_bounds__(kBlock) void moe_route_kernel(const uint16_t* __restrict__ h,
+                                                           const uint16_t* __restrict__ wr,
+                                                           int32_t* __restrict__ ids, float* __restrict__ p, int T,
+                                                           int H, int E, int k, int norm) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int t = blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
+    if (t >= T) return;  // whole waves leave; no block-level barrier below
+    const uint4* hr = reinterpret_cast<const uint4*>(h + (size_t)t * H);
+    const int nvec = H >> 3;
+    // logit of expert e lands in lane e % 64, slot e / 64
+    float lg[kEPL];
+#pragma unroll
+    for (int s = 0; s < kEPL; ++s) lg[s] = -INFINITY;
+    for (int e = 0; e < E; ++e) {
+        const uint4* we = reinterpret_cast<const uint4*>(wr + (size_t)e * H);
+        float acc = 0.f;
+        for (int v = lane; v < nvec; v += kWave) {
+            float a[8], b[8];
+            unpack8(hr[v], a);
+            unpack8(we[v], b);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc = fmaf(a[j], b[j], acc);
+        }
+        acc = wave_sum(acc);
+        if (!(acc == acc)) acc = -INFINITY;  // a NaN logit never wins, and never blocks the selection
+#pragma unroll
+        for (int s = 0; s < kEPL; ++s)
+            if ((e >> 6) == s && (e & 63) == lane) lg[s] = acc;
+    }
+    float mx = -INFINITY;
+#pragma unroll
+    for (int s = 0; s < kEPL; ++s) mx = fmaxf(mx, lg[s]);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m, kWave));
+    if (mx == -INFINITY) mx = 0.f;
+    float pr[kEPL], sum = 0.f;
+#pragma unroll
+    for (int s = 0; s < kEPL; ++s) {
+        pr[s] = (s * kWave + lane < E) ? expf(lg[s] - mx) : 0.f;
+        sum += pr[s];
+    }
+    sum = wave_sum(sum);
+#pragma unroll
+    for (int s = 0; s < kEPL; ++s) pr[s] = pr[s] / sum;
+    // k rounds of arg-max over the experts not taken yet: the largest
+    // probability, the lowest id among equals.  Every round finds one (k <= E
+    // and -inf == -inf compares equal), so ids are distinct and in [0, E).
+    uint32_t taken = 0u;
+    float sel[kEPL];  // rank j's probability in lane j % 64, slot j / 64
+#pragma unroll
+    for (int s = 0; s < kEPL; ++s) sel[s] = 0.f;
+    for (int j = 0; j < k; ++j) {
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int s = 0; s < kEPL; ++s) {
+            const int e = s * kWave + lane;
+            if (e < E && !((taken >> s) & 1u)) {
+                const float v = pr[s] == pr[s] ? pr[s] : -INFINITY;
+                if (v > bv || (v == bv && e < bi)) { bv = v; bi = e; }
+            }
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const float ov = __shfl_xor(bv, m, kWave);
+            const int oi = __shfl_xor(bi, m, kWave);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        bi = min(max(bi, 0), E - 1);
+        if ((bi & 63) == lane) taken |= 1u << (bi >> 6);
+        if (lane == 0) ids[(size_t)t * k + j] = bi;
+#pragma unroll
+        for (int s = 0; s < kEPL; ++s)
+            if ((j >> 6) == s && (j & 63) == lane) sel[s] = bv > 0.f ? bv : 0.f;
+    }
+    float den = 1.f;
+    if (norm) {
+        // a butterfly sum: equal probabilities (k a power of two) add up
+        // exactly, so p comes out as exactly 1 / k
+        float sacc = 0.f;
+#pragma unroll
+        for (int s = 0; s < kEPL; ++s) sacc += sel[s];
+        den = wave_sum(sacc);
+        if (!(den > 0.f)) den = 1.f;
+    }
+#pragma unroll
+    for (int s = 0; s < kEPL; ++s) {
+        const int j = s * kWave + lane;
+        if (j < k) p[(size_t)t * k + j] = sel[s] / den;
+    }
+}
+
+// ------------------------------------------------------- 2. count, 3. scatter
+__global__ __launch_bounds__(kWave) void moe_count_kernel(const int32_t* __restrict__ ids, int32_t* __restrict__ cnt,
+                                                          int P) {
+    const int e = blockIdx.x, lane = threadIdx.x;
+    int c = 0;
+    for (int i = lane; i < P; i += kWave) c += ids[i] == e;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, kWave);
+    if (lane == 0) cnt[e] = c;
+}
+
+// tiles: int32 [max_tiles][3] = (expert, first grouped row, rows)
+__global__ __launch_bounds__(kWave) void moe_scatter_kernel(const int32_t* __restrict__ ids,
+                                                            const int32_t* __restrict__ cnt,
+                                                            int32_t* __restrict__ offs, int32_t* __restrict__ perm,
+                                                            int32_t* __restrict__ tiles, int32_t* __restrict__ ntiles,
+                                                            int P, int E, int MT, int max_tiles) {
+    const int e = blockIdx.x, lane = threadIdx.x;
+    int before = 0, tbefore = 0;
+    for (int i = lane; i < e; i += kWave) {
+        const int c = cnt[i];
+        before += c;
+        tbefore += (c + MT - 1) / MT;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        before += __shfl_xor(before, m, kWave);
+        tbefore += __shfl_xor(tbefore, m, kWave);
+    }
+    const int mine = cnt[e];
+    const int nt = (mine + MT - 1) / MT;
+    if (lane == 0) {
+        offs[e] = before;
+        if (e == E - 1) {
+            offs[E] = before + mine;
+            *ntiles = min(tbefore + nt, max_tiles);
+        }
+    }
+    for (int i = lane; i < nt; i += kWave) {
+        if (tbefore + i < max_tiles) {
+            int32_t* te = tiles + 3 * (size_t)(tbefore + i);
+            te[0] = e;
+            te[1] = before + i * MT;
+            te[2] = min(MT, mine - i * MT);
+        }
+    }
+    // stable placement: pairs of this expert in ascending pair index
+    int placed = 0;
+    for (int i0 = 0; i0 < P; i0 += kWave) {
+        const int i = i0 + lane;
+        const bool hit = i < P && ids[i] == e;
+        const unsigned long long bal = __ballot(hit);
+        if (hit) {
+            const int dst = before + placed + __popcll(bal & ((1ull << lane) - 1ull));
+            if (dst < P) perm[dst] = i;
+        }
+        placed += __popcll(bal);
+    }
+}
+
+// --------------------------------------------------- 4. gate/up, 5. down GEMM
+// Y[rows of a tile][columns of the block] = X[rows][K] . W[e][columns][K]^T.
+// A wave owns two 16-column weight fragments: columns c0 + 16 wv and the same
+// + `second` (gate/up: the up rows, I further down; down: 64 columns on).
+// RT 16-row subtiles per tile (MT = 16 RT).  X rows reach LDS in 64-deep K
+// chunks, [row][8 x 16 B] with chunk j of row r in slot j ^ (r & 7)
+// (conflict-free ds_read_b128 of the B operand), double buffered: chunk c + 1
+// is loaded to registers before chunk c's MFMAs and stored after them.
+template <int RT, bool SWIGLU>
+__global__ __launch_bounds__(kBlock) void moe_gemm_kernel(const uint16_t* __restrict__ x,
+                                                          const uint16_t* __restrict__ w,
+                                                          const int32_t* __restrict__ perm,
+                                                          const int32_t* __restrict__ tiles,
+                                                          const int32_t* __restrict__ ntiles, uint16_t* __restrict__ act,
+                                                          float* __restrict__ y, int P, int K, int N, int topk) {
+    constexpr int MT = RT * 16;
+    constexpr int XP = MT * 8 / kBlock > 0 ? MT * 8 / kBlock : 1;  // 16-B pieces per thread per chunk
+    static_assert(MT * 8 % kBlock == 0 || MT * 8 < kBlock, "row tile");
+    __shared__ uint4 lds[2 * MT * 8];
+    __shared__ int32_t srow[MT];
+
+    const int tile = blockIdx.y;
+    if (tile >= *ntiles) return;
+    const int e = tiles[3 * (size_t)tile], first = tiles[3 * (size_t)tile + 1], rows = tiles[3 * (size_t)tile + 2];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+    const int l16 = lane & 15, g = lane >> 4;
+    // source row of X per tile row (rows past the tile repeat its first row;
+    // their results are never stored): gate/up gathers token perm / k, down
+    // reads act in grouped order
+    if (tid < MT) {
+        const int gr = first + (tid < rows ? tid : 0);
+        const int pair = min(max(perm[min(gr, P - 1)], 0), P - 1);
+        srow[tid] = SWIGLU ? pair / topk : min(gr, P - 1);
+    }
+    __syncthreads();
+
+    // weight rows of this wave's two fragments.  SWIGLU: N = I, w [E][2 I][K];
+    // else N = H, w [E][H][K]
+    const int cblk = SWIGLU ? 64 : 128;
+    const int c0 = blockIdx.x * cblk + wv * 16;
+    const int c1 = SWIGLU ? c0 : c0 + 64;          // output column of fragment 1
+    const bool f1 = SWIGLU || c1 < N;              // fragment 1 exists (H % 128 == 64: the last block's does not)
+    const size_t wrows = SWIGLU ? 2 * (size_t)N : (size_t)N;
+    const uint16_t* wbase = w + (size_t)e * wrows * K;
+    const uint16_t* wa0 = wbase + (size_t)(c0 + l16) * K + g * 8;
+    const uint16_t* wa1 = wbase + (size_t)(SWIGLU ? N + c0 + l16 : (f1 ? c1 + l16 : c0 + l16)) * K + g * 8;
+
+    const uint16_t* xsrc[XP];
+    int xdst[XP];
+    bool xon[XP];
+#pragma unroll
+    for (int i = 0; i < XP; ++i) {
+        const int piece = tid + i * kBlock;        // row = piece / 8, logical 16-B chunk = piece % 8
+        xon[i] = piece < MT * 8;
+        const int r = xon[i] ? piece >> 3 : 0, j = piece & 7;
+        xsrc[i] = x + (size_t)srow[r] * K + j * 8;
+        xdst[i] = r * 8 + (j ^ (r & 7));
+    }
+
+    f32x4_t acc[2][RT];
+#pragma unroll
+    for (int f = 0; f < 2; ++f)
+#pragma unroll
+        for (int t = 0; t < RT; ++t) acc[f][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+    const int chunks = K / 64;
+    uint4 xr[XP], a[2][2], an[2][2];
+#pragma unroll
+    for (int i = 0; i < XP; ++i)
+        if (xon[i]) lds[xdst[i]] = *reinterpret_cast<const uint4*>(xsrc[i]);
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        a[0][kk] = *reinterpret_cast<const uint4*>(wa0 + kk * 32);
+        a[1][kk] = *reinterpret_cast<const uint4*>(wa1 + kk * 32);
+    }
+    __syncthreads();
+    for (int c = 0; c < chunks; ++c) {
+        const bool more = c + 1 < chunks;
+        if (more) {
+#pragma unroll
+            for (int i = 0; i < XP; ++i)
+                if (xon[i]) xr[i] = *reinterpret_cast<const uint4*>(xsrc[i] + (c + 1) * 64);
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                an[0][kk] = *reinterpret_cast<const uint4*>(wa0 + (c + 1) * 64 + kk * 32);
+                an[1][kk] = *reinterpret_cast<const uint4*>(wa1 + (c + 1) * 64 + kk * 32);
+            }
+        }
+        const uint4* xl = lds + (c & 1) * (MT * 8);
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+#pragma unroll
+            for (int t = 0; t < RT; ++t) {
+                const int r = 16 * t + l16;
+                const bf16x8_t b = as_bf16x8(xl[r * 8 + ((4 * kk + g) ^ (r & 7))]);
+                acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(a[0][kk]), b, acc[0][t], 0, 0, 0);
+                acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(a[1][kk]), b, acc[1][t], 0, 0, 0);
+            }
+        }
+        if (more) {
+            uint4* xs = lds + ((c + 1) & 1) * (MT * 8);
+#pragma unroll
+            for (int i = 0; i < XP; ++i)
+                if (xon[i]) xs[xdst[i]] = xr[i];
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                a[0][kk] = an[0][kk];
+                a[1][kk] = an[1][kk];
+            }
+        }
+        // one barrier per chunk: chunk c + 1 is complete, and nobody still
+        // reads the buffer that chunk c + 2 will overwrite after the next one
+        __syncthreads();
+    }
+
+    // lane (l16, g) holds Y[tile row 16 t + l16][fragment column 4 g + i]
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+        const int r = 16 * t + l16;
+        if (r >= rows) continue;
+        const int gr = first + r;
+        if (gr >= P) continue;
+        if constexpr (SWIGLU) {
+            float o[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[i] = silu(acc[0][t][i]) * acc[1][t][i];
+            *reinterpret_cast<uint2*>(act + (size_t)gr * N + c0 + 4 * g) = pack4(o);
+        } else {
+            const int pair = min(max(perm[gr], 0), P - 1);
+            float* dst = y + (size_t)pair * N;
+            *reinterpret_cast<float4*>(dst + c0 + 4 * g) =
+                make_float4(acc[0][t][0], acc[0][t][1], acc[0][t][2], acc[0][t][3]);
+            if (f1)
+                *reinterpret_cast<float4*>(dst + c1 + 4 * g) =
+                    make_float4(acc[1][t][0], acc[1][t][1], acc[1][t][2], acc[1][t][3]);
+        }
+    }
+}
+
+// ------------------------------------------------------------- 6. combine
+// m = bf16(sum_j p[t, j] * y[t k + j]) in rank order, then add_rmsnorm_kernel
+// (dmcp_kernels.hip) on m, operation for operation: h = m (+ residual),
+// residual <- bf16(h), out = h * rsqrt(mean(h^2) + eps) * w.  w == nullptr:
+// no norm (out <- m when there is no residual either).
+template <int VPT>
+__global__ __launch_bounds__(kBlock) void moe_combine_kernel(const float* __restrict__ y, const float* __restrict__ p,
+                                                             uint16_t* __restrict__ residual,
+                                                             const uint16_t* __restrict__ w,
+                                                             uint16_t* __restrict__ out, int H, int topk, float eps) {
+    const int row = blockIdx.x;
+    const int nvec = H >> 3;
+    uint4* rr = residual ? reinterpret_cast<uint4*>(residual + (size_t)row * H) : nullptr;
+    const uint4* wr = reinterpret_cast<const uint4*>(w);
+    const float* pr = p + (size_t)row * topk;
+    const float* yr = y + (size_t)row * topk * H;
+    float h[VPT][8];
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+        const int idx = threadIdx.x + i * kBlock;
+        if (idx < nvec) {
+            float m[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < topk; ++j) {
+                const float pj = pr[j];
+                const float4 lo = *reinterpret_cast<const float4*>(yr + (size_t)j * H + idx * 8);
+                const float4 hi = *reinterpret_cast<const float4*>(yr + (size_t)j * H + idx * 8 + 4);
+                m[0] = fmaf(pj, lo.x, m[0]); m[1] = fmaf(pj, lo.y, m[1]);
+                m[2] = fmaf(pj, lo.z, m[2]); m[3] = fmaf(pj, lo.w, m[3]);
+                m[4] = fmaf(pj, hi.x, m[4]); m[5] = fmaf(pj, hi.y, m[5]);
+                m[6] = fmaf(pj, hi.z, m[6]); m[7] = fmaf(pj, hi.w, m[7]);
+            }
+            uint4 packed = pack8(m);
+            unpack8(packed, h[i]);  // the MLP output as the bf16 row add_rmsnorm would be given
+            if (rr) {
+                float r[8];
+                unpack8(rr[idx], r);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) h[i][j] += r[j];
+                packed = pack8(h[i]);
+                rr[idx] = packed;
+                unpack8(packed, h[i]);
+            }
+            if (!w && out) reinterpret_cast<uint4*>(out + (size_t)row * H)[idx] = packed;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) ss += h[i][j] * h[i][j];
+        }
+    }
+    if (!w) return;  // uniform: a kernel argument
+    __shared__ float red[kBlock / kWave];
+    ss = wave_sum(ss);
+    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = ss;
+    __syncthreads();
+    float tot = 0.f;
+#pragma unroll
+    for (int k = 0; k < kBlock / kWave; ++k) tot += red[k];
+    const float inv = rsqrtf(tot / (float)H + eps);
+    uint4* orow = reinterpret_cast<uint4*>(out + (size_t)row * H);
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+        const int idx = threadIdx.x + i * kBlock;
+        if (idx < nvec) {
+            float wf[8], o[8];
+            unpack8(wr[idx], wf);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = h[i][j] * inv * wf[j];
+            orow[idx] = pack8(o);
+        }
+    }
+}
+
+bool moe_shape_ok(int T, int H, int I, int E, int k, int MT) {
+    return T > 0 && H > 0 && I > 0 && H % 64 == 0 && I % 64 == 0 && H <= 8192 && E >= 1 && E <= kMaxExperts &&
+           k >= 1 && k <= E && (MT == 32 || MT == 128) && (long long)T * k < (1ll << 30);
+}
+
+template <int RT>
+void launch_gemms(const uint16_t* h, const uint16_t* wgu, const uint16_t* wdown, const int32_t* perm,
+                  const int32_t* tiles, const int32_t* ntiles, uint16_t* act, float* y, int P, int H, int I, int k,
+                  int max_tiles, hipStream_t st) {
+    moe_gemm_kernel<RT, true><<<dim3(I / 64, max_tiles), kBlock, 0, st>>>(h, wgu, perm, tiles, ntiles, act, nullptr,
+                                                                           P, H, I, k);
+    moe_gemm_kernel<RT, false><<<dim3((H + 127) / 128, max_tiles), kBlock, 0, st>>>(act, wdown, perm, tiles, ntiles,
+                                                                                     nullptr, y, P, I, H, k);
+}
+
+}  // namespace
+
+extern "C" {
+
+// h [T, H] bf16, wr [E, H] bf16 -> ids int32 [T, k], p fp32 [T, k]
+int dmcp_moe_route(const void* h, const void* wr, void* ids, void* p, int T, int H, int E, int k, int norm,
+                   void* stream) {
+    if (!moe_shape_ok(T, H, 64, E, k, 32)) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const int wpb = kBlock / kWave;
+    moe_route_kernel<<<(T + wpb - 1) / wpb, kBlock, 0, st>>>((const uint16_t*)h, (const uint16_t*)wr, (int32_t*)ids,
+                                                             (float*)p, T, H, E, k, norm);
+    return (int)hipGetLastError();
+}
+
+// The whole block.  Scratch (the caller's workspace): ids / p [T k], cnt [E],
+// offs [E + 1], perm [T k], tiles [3 (ceil(T k / MT) + E)], ntiles [1],
+// act bf16 [T k, I], y fp32 [T k, H].  residual / norm_w / out: the combine's
+// add_rmsnorm contract (norm_w null: out <- m, or residual += m).
+int dmcp_moe_mlp(const void* h, const void* wr, const void* wgu, const void* wdown, void* ids, void* p, void* cnt,
+                 void* offs, void* perm, void* tiles, void* ntiles, void* act, void* y, void* residual,
+                 const void* norm_w, void* out, int T, int H, int I, int E, int k, int norm, int MT, float eps,
+                 void* stream) {
+    if (!moe_shape_ok(T, H, I, E, k, MT)) return (int)hipErrorInvalidValue;
+    if (!norm_w && !residual && !out) return (int)hipErrorInvalidValue;
+    if (norm_w && !out) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const int P = T * k;
+    const int max_tiles = (P + MT - 1) / MT + E;
+    if (max_tiles > 65535) return (int)hipErrorInvalidValue;  // grid.y
+    const int wpb = kBlock / kWave;
+    moe_route_kernel<<<(T + wpb - 1) / wpb, kBlock, 0, st>>>((const uint16_t*)h, (const uint16_t*)wr, (int32_t*)ids,
+                                                             (float*)p, T, H, E, k, norm);
+    moe_count_kernel<<<E, kWave, 0, st>>>((const int32_t*)ids, (int32_t*)cnt, P);
+    moe_scatter_kernel<<<E, kWave, 0, st>>>((const int32_t*)ids, (const int32_t*)cnt, (int32_t*)offs, (int32_t*)perm,
+                                            (int32_t*)tiles, (int32_t*)ntiles, P, E, MT, max_tiles);
+    if (MT == 32)
+        launch_gemms<2>((const uint16_t*)h, (const uint16_t*)wgu, (const uint16_t*)wdown, (const int32_t*)perm,
+                        (const int32_t*)tiles, (const int32_t*)ntiles, (uint16_t*)act, (float*)y, P, H, I, k,
+                        max_tiles, st);
+    else
+        launch_gemms<8>((const uint16_t*)h, (const uint16_t*)wgu, (const uint16_t*)wdown, (const int32_t*)perm,
+                        (const int32_t*)tiles, (const int32_t*)ntiles, (uint16_t*)act, (float*)y, P, H, I, k,
+                        max_tiles, st);
+    const int vpt = (H / 8 + kBlock - 1) / kBlock;
+    const float* yy = (const float*)y;
+    const float* pp = (const float*)p;
+    uint16_t* rr = (uint16_t*)residual;
+    const uint16_t* ww = (const uint16_t*)norm_w;
+    uint16_t* oo = (uint16_t*)out;
+    if (vpt == 1) moe_combine_kernel<1><<<T, kBlock, 0, st>>>(yy, pp, rr, ww, oo, H, k, eps);
+    else if (vpt == 2) moe_combine_kernel<2><<<T, kBlock, 0, st>>>(yy, pp, rr, ww, oo, H, k, eps);
+    else moe_combine_kernel<4><<<T, kBlock, 0, st>>>(yy, pp, rr, ww, oo, H, k, eps);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

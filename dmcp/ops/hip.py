@@ -133,6 +133,11 @@ def lib() -> ctypes.CDLL:
             "dmcp_prefill_varlen_scaled": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_long,
                                             _f, _vp, _vp, _vp, _vp, _vp], _i),
             "dmcp_kv_fork_scaled": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp], _i),
+            # the routed expert MLP (csrc/moe.hip): h, router, ids, p, T, H, E, k, norm_topk
+            "dmcp_moe_route": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
+            # h, router, w_gu, w_down, 9 workspace parts (ids, p, cnt, offs, perm, tiles, ntiles, act, y),
+            # residual, norm_w, out, T, H, I, E, k, norm_topk, row tile, eps
+            "dmcp_moe_mlp": ([_vp] * 16 + [_i, _i, _i, _i, _i, _i, _i, _f, _vp], _i),
         }
         for name, (args, res) in sigs.items():
             try:
@@ -1986,3 +1991,127 @@ def _rope_kv(fam: _Family, ops: tuple, pos: torch.Tensor, slot: torch.Tensor, co
                                      _ptr(k_cache), _ptr(v_cache), M, n_q_heads, Hkv, D, max_seq, cos_sin.shape[0],
                                      slots, kv8, _stream(), _ptr(bias)), "dmcp_reduce_rope_kv")
     return q_out
+
+
+# ------------------------------------------------- routed expert MLP (csrc/moe.hip)
+MOE_MAX_EXPERTS = 256
+MOE_ROW_TILES = (32, 128)   # rows of one expert per GEMM block: few rows per expert (decode), many (prefill)
+MOE_MAX_PAIRS = 1 << 20     # (row, rank) pairs per launch: the tile grid's y extent stays below 65,536
+
+
+def moe_supported(hidden: int, inter: int, n_experts: int, top_k: int) -> bool:
+    """The routed expert MLP's shape contract: 64-deep K chunks of both GEMMs
+    (hidden, intermediate multiples of 64), the combine's row in one block
+    (hidden <= 8192), the routing wave's four expert slots per lane."""
+    return (hidden > 0 and inter > 0 and hidden % 64 == 0 and inter % 64 == 0 and hidden <= 8192
+            and 1 <= top_k <= n_experts <= MOE_MAX_EXPERTS)
+
+
+def moe_row_tile(rows: int, n_experts: int, top_k: int) -> int:
+    """The GEMMs' row tile for a launch of ``rows`` rows: 128 once an expert
+    sees 64 rows on average (each block then streams its weight columns for
+    4x the rows), else 32.  The switch point is reasoned (below it most
+    128-row tiles would be under half full), not chosen by an A/B."""
+    return MOE_ROW_TILES[1] if rows * top_k >= 64 * n_experts else MOE_ROW_TILES[0]
+
+
+def _moe_layout(rows: int, hidden: int, inter: int, n_experts: int, top_k: int) -> tuple:
+    """Byte offsets of the workspace parts (ids, p, cnt, offs, perm, tiles,
+    ntiles, act, y) for a launch of ``rows`` rows, and the total size; every
+    part 256-byte aligned.  The tile table is sized for the smaller row tile."""
+    P = rows * top_k
+    tiles = -(-P // MOE_ROW_TILES[0]) + n_experts
+    sizes = (4 * P, 4 * P, 4 * n_experts, 4 * (n_experts + 1), 4 * P, 12 * tiles, 4, 2 * P * inter, 4 * P * hidden)
+    offs, at = [], 0
+    for s in sizes:
+        offs.append(at)
+        at += -(-s // 256) * 256
+    return tuple(offs), at
+
+
+def moe_workspace(rows: int, hidden: int, inter: int, n_experts: int, top_k: int, device) -> torch.Tensor:
+    """The scratch of :func:`moe_mlp` for launches of up to ``rows`` rows
+    (uint8): routing, the grouping tables, act bf16 [rows k, I] and the
+    per-pair down rows fp32 [rows k, H].  Allocated once by the model."""
+    if not moe_supported(hidden, inter, n_experts, top_k) or rows <= 0 or rows * top_k > MOE_MAX_PAIRS:
+        raise HipOpsError(f"moe_workspace: unsupported shape (rows {rows}, hidden {hidden}, inter {inter}, "
+                          f"experts {n_experts}, top_k {top_k})")
+    return torch.empty(_moe_layout(rows, hidden, inter, n_experts, top_k)[1], dtype=torch.uint8, device=device)
+
+
+def _moe_args(h, w_router, w_gu, w_down, top_k, name) -> tuple:
+    _req(h, torch.bfloat16, f"{name}.h")
+    _req(w_router, torch.bfloat16, f"{name}.w_router")
+    if h.dim() != 2 or w_router.dim() != 2 or h.shape[1] != w_router.shape[1]:
+        raise HipOpsError(f"{name}: h {tuple(h.shape)} does not match the router {tuple(w_router.shape)}")
+    T, H = h.shape
+    E = w_router.shape[0]
+    inter = 64
+    if w_gu is not None:
+        _req(w_gu, torch.bfloat16, f"{name}.w_gu")
+        _req(w_down, torch.bfloat16, f"{name}.w_down")
+        inter = w_down.shape[2] if w_down.dim() == 3 else -1
+        if tuple(w_gu.shape) != (E, 2 * inter, H) or tuple(w_down.shape) != (E, H, inter):
+            raise HipOpsError(f"{name}: w_gu {tuple(w_gu.shape)} / w_down {tuple(w_down.shape)} are not "
+                              f"[E, 2I, H] / [E, H, I] for E {E}, H {H}")
+    if not isinstance(top_k, int) or not moe_supported(H, inter, E, top_k):
+        raise HipOpsError(f"{name}: unsupported shape (hidden {H}, inter {inter}, experts {E}, top_k {top_k}); "
+                          f"see moe_supported")
+    if T * top_k > MOE_MAX_PAIRS:
+        raise HipOpsError(f"{name}: {T} rows x top_k {top_k} exceed {MOE_MAX_PAIRS} pairs per launch")
+    return T, H, inter, E
+
+
+def moe_route(h: torch.Tensor, w_router: torch.Tensor, top_k: int, norm_topk: bool) -> tuple:
+    """(ids int32 [T, k], p fp32 [T, k]): the routing kernel of :func:`moe_mlp` alone."""
+    T, H, _, E = _moe_args(h, w_router, None, None, top_k, "moe_route")
+    ids = torch.empty((T, top_k), dtype=torch.int32, device=h.device)
+    p = torch.empty((T, top_k), dtype=torch.float32, device=h.device)
+    if T:
+        _check(lib().dmcp_moe_route(_ptr(h), _ptr(w_router), _ptr(ids), _ptr(p), T, H, E, top_k, int(bool(norm_topk)),
+                                    _stream()), "dmcp_moe_route")
+    return ids, p
+
+
+def moe_mlp(h: torch.Tensor, w_router: torch.Tensor, w_gu: torch.Tensor, w_down: torch.Tensor, top_k: int,
+            norm_topk: bool, residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None,
+            eps: float = 0.0, workspace: Optional[torch.Tensor] = None,
+            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The routed expert MLP (Qwen3-MoE sparse block) of bf16 rows ``h`` [T, H]:
+    top-k routing, a device-side counting sort of the (row, rank) pairs by
+    expert, the grouped gate/up GEMM with SwiGLU, the grouped down GEMM and
+    the weighted combine, fused with ``add_rmsnorm(m, norm_w, eps,
+    residual=residual)`` (``residual`` alone: residual += m; neither: m is
+    returned) -- six launches with host-known grids, capturable, no atomics.
+    ``workspace``: :func:`moe_workspace` for at least T rows (allocated per
+    call when None; a model passes its own)."""
+    T, H, inter, E = _moe_args(h, w_router, w_gu, w_down, top_k, "moe_mlp")
+    offs, need = _moe_layout(max(T, 1), H, inter, E, top_k)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=h.device)
+    _req(workspace, torch.uint8, "moe_mlp.workspace")
+    if workspace.numel() < need or workspace.device != h.device:
+        raise HipOpsError(f"moe_mlp: workspace holds {workspace.numel()} bytes on {workspace.device}, "
+                          f"{T} rows need {need} on {h.device}")
+    if residual is not None:
+        _req(residual, torch.bfloat16, "moe_mlp.residual")
+        if residual.shape != h.shape:
+            raise HipOpsError("moe_mlp: residual shape mismatch")
+    if norm_w is not None:
+        _req(norm_w, torch.bfloat16, "moe_mlp.norm_w")
+        if norm_w.numel() != H:
+            raise HipOpsError(f"moe_mlp: norm_w holds {norm_w.numel()} elements, a row has {H}")
+    if norm_w is not None or residual is None:
+        out = torch.empty_like(h) if out is None else out
+        _req_out(out, torch.bfloat16, T * H, "moe_mlp.out")
+    else:
+        out = None  # residual += m: nothing else is written
+    if T:
+        base = workspace.data_ptr()
+        if base % 16:
+            raise HipOpsError("moe_mlp: workspace must be 16-byte aligned")
+        parts = [ctypes.c_void_p(base + o) for o in offs]
+        _check(lib().dmcp_moe_mlp(_ptr(h), _ptr(w_router), _ptr(w_gu), _ptr(w_down), *parts, _ptr(residual),
+                                  _ptr(norm_w), _ptr(out), T, H, inter, E, top_k, int(bool(norm_topk)),
+                                  moe_row_tile(T, E, top_k), float(eps), _stream()), "dmcp_moe_mlp")
+    return out if out is not None else residual

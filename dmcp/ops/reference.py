@@ -996,3 +996,90 @@ def pgemm_qkv(aq, as_, wq, ws, pos, slot, cos_sin, k_cache, v_cache, n_q_heads: 
               q_out: Optional[torch.Tensor] = None) -> torch.Tensor:
     qkv = _pgemm_f32(aq, as_, wq, ws).to(torch.bfloat16)
     return rope_kv(qkv, pos, slot, cos_sin, k_cache, v_cache, n_q_heads, q_out)
+
+
+# ---- routed expert MLP (Qwen3-MoE sparse block; csrc/moe.hip).  For each row
+# of h [T, H]: router logits h . Wr^T over E experts, softmax over all E, the k
+# largest probabilities (a tie goes to the lower expert id), optionally
+# renormalised to sum 1, then y = sum_j p_j * down_e(silu(gate_e(h)) * up_e(h))
+# over the chosen experts in rank order.  w_gu [E, 2 I, H] holds an expert's
+# gate rows first, then its up rows (the dense wgu convention); w_down [E, H, I].
+def moe_route_math(h: torch.Tensor, w_router: torch.Tensor, top_k: int, norm_topk: bool) -> tuple:
+    """(ids int64 [T, k], p [T, k]) in the dtype of ``h`` (fp32 or fp64):
+    the definition, shared by the bf16 op, the model's fp32 reference forward
+    and the tests' fp64 oracle."""
+    E = w_router.shape[0]
+    if not 1 <= top_k <= E:
+        raise ValueError(f"moe_route: top_k {top_k} outside [1, {E}] (num_experts)")
+    prob = torch.softmax(h @ w_router.t(), dim=-1)
+    # a stable descending sort keeps the lower id first among equal probabilities
+    order = torch.sort(prob, dim=-1, descending=True, stable=True).indices[:, :top_k]
+    p = prob.gather(1, order)
+    if norm_topk:
+        p = p / p.sum(-1, keepdim=True)
+    return order, p
+
+
+def moe_mlp_math(h: torch.Tensor, w_router: torch.Tensor, w_gu: torch.Tensor, w_down: torch.Tensor, top_k: int,
+                 norm_topk: bool, round_act=None) -> torch.Tensor:
+    """y [T, H] in the dtype of ``h`` (fp32 or fp64; weights of that dtype).
+    ``round_act``: applied to silu(gate) * up (the kernel keeps it in bf16)."""
+    ids, p = moe_route_math(h, w_router, top_k, norm_topk)
+    inter = w_down.shape[2]
+    y = torch.zeros_like(h)
+    for j in range(top_k):  # rank order
+        for e in ids[:, j].unique().tolist():
+            rows = (ids[:, j] == e).nonzero()[:, 0]
+            x = h[rows]
+            gu = x @ w_gu[e].t()
+            g, u = gu[:, :inter], gu[:, inter:]
+            act = g / (1.0 + torch.exp(-g)) * u
+            if round_act is not None:
+                act = round_act(act)
+            y[rows] += p[rows, j:j + 1] * (act @ w_down[e].t())
+    return y
+
+
+def _moe_check(h, w_router, w_gu, w_down, top_k, name):
+    E, H = w_router.shape
+    if h.dim() != 2 or h.shape[1] != H:
+        raise ValueError(f"{name}: h {tuple(h.shape)} does not match the router {tuple(w_router.shape)}")
+    if not 1 <= top_k <= E:
+        raise ValueError(f"{name}: top_k {top_k} outside [1, {E}] (num_experts)")
+    if w_gu is not None:
+        inter = w_down.shape[2] if w_down.dim() == 3 else -1
+        if tuple(w_gu.shape) != (E, 2 * inter, H) or tuple(w_down.shape) != (E, H, inter):
+            raise ValueError(f"{name}: w_gu {tuple(w_gu.shape)} / w_down {tuple(w_down.shape)} are not "
+                             f"[E, 2I, H] / [E, H, I] for E {E}, H {H}")
+
+
+def moe_route(h: torch.Tensor, w_router: torch.Tensor, top_k: int, norm_topk: bool) -> tuple:
+    """(ids int32 [T, k], p fp32 [T, k]) of bf16 rows ``h`` [T, H] under the
+    bf16 router ``w_router`` [E, H]; logits, softmax and selection in fp32."""
+    _moe_check(h, w_router, None, None, top_k, "moe_route")
+    ids, p = moe_route_math(h.float(), w_router.float(), int(top_k), bool(norm_topk))
+    return ids.to(torch.int32), p
+
+
+def moe_mlp(h: torch.Tensor, w_router: torch.Tensor, w_gu: torch.Tensor, w_down: torch.Tensor, top_k: int,
+            norm_topk: bool, residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None,
+            eps: float = 0.0, workspace: Optional[torch.Tensor] = None,
+            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The routed expert MLP of bf16 rows ``h`` [T, H] (already normalised),
+    with what follows it in the model: m = bf16(y), then
+    ``add_rmsnorm(m, norm_w, eps, residual=residual)`` when ``norm_w`` is
+    given (``residual`` updated in place, the normalised rows returned);
+    ``residual`` alone: residual += m, returned; neither: m.  ``workspace``
+    is the GPU kernels' scratch (:func:`dmcp.ops.hip.moe_workspace`), unused here."""
+    _moe_check(h, w_router, w_gu, w_down, top_k, "moe_mlp")
+    m = moe_mlp_math(h.float(), w_router.float(), w_gu.float(), w_down.float(), int(top_k), bool(norm_topk),
+                     round_act=lambda a: a.to(torch.bfloat16).float()).to(h.dtype)
+    if norm_w is not None:
+        return add_rmsnorm(m, norm_w, eps, residual=residual, out=out)
+    if residual is not None:
+        residual.copy_((m.float() + residual.float()).to(residual.dtype))
+        return residual
+    if out is not None:
+        out.copy_(m)
+        return out
+    return m

@@ -561,6 +561,53 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
     return root
 
 
+def qwen3_moe_checkpoint(root: str, n_experts: int = 8, experts_per_tok: int = 2, moe_intermediate: int = 128,
+                         norm_topk: bool = True, experts_key: str = "num_experts", seed: int = 11,
+                         device: str = "cuda", **kw) -> str:
+    """A Qwen3-MoE checkpoint directory in the hub layout: what
+    :func:`llama_checkpoint` writes for ``model_type="qwen3"`` (``kw`` goes
+    there: geometry, tokenizer, tied embeddings, ...) with every layer's dense
+    MLP replaced by a router ``mlp.gate.weight`` [E, hidden] and
+    ``mlp.experts.{e}.{gate,up,down}_proj.weight``, drawn from a generator of
+    their own.  The router is drawn at std 1 / sqrt(hidden) x 2 so the top-k
+    probabilities differ visibly (a flat router would hide a loader that
+    ignored ``norm_topk_prob`` or shuffled the experts).  ``experts_key``:
+    ``num_experts`` (hub configs) or ``num_local_experts`` (what newer
+    ``transformers`` writes)."""
+    import json
+
+    import torch
+    from safetensors.torch import load_file, save_file
+    llama_checkpoint(root, seed=seed, device=device, model_type="qwen3", qk_norm=True, **kw)
+    f = os.path.join(root, "model.safetensors")
+    t = load_file(f)
+    with open(os.path.join(root, "config.json")) as fh:
+        cfg = json.load(fh)
+    hidden, layers = cfg["hidden_size"], cfg["num_hidden_layers"]
+    g = torch.Generator(device=device).manual_seed(seed + 1000)
+
+    def rnd(shape, std):
+        return (torch.randn(shape, generator=g, device=device) * std).to(torch.bfloat16).cpu()
+    out_std = 0.02 / (2 * layers) ** 0.5
+    for i in range(layers):
+        p = f"model.layers.{i}.mlp."
+        for n in ("gate_proj", "up_proj", "down_proj"):
+            del t[p + n + ".weight"]
+        t[p + "gate.weight"] = rnd((n_experts, hidden), 2.0 / hidden ** 0.5)
+        for e in range(n_experts):
+            t[f"{p}experts.{e}.gate_proj.weight"] = rnd((moe_intermediate, hidden), 0.02)
+            t[f"{p}experts.{e}.up_proj.weight"] = rnd((moe_intermediate, hidden), 0.02)
+            t[f"{p}experts.{e}.down_proj.weight"] = rnd((hidden, moe_intermediate), out_std)
+    save_file(t, f)
+    cfg.update({"model_type": "qwen3_moe", "architectures": ["Qwen3MoeForCausalLM"], experts_key: n_experts,
+                "num_experts_per_tok": experts_per_tok, "moe_intermediate_size": moe_intermediate,
+                "norm_topk_prob": bool(norm_topk), "decoder_sparse_step": 1, "mlp_only_layers": [],
+                "output_router_logits": False, "router_aux_loss_coef": 0.001})
+    with open(os.path.join(root, "config.json"), "w") as fh:
+        json.dump(cfg, fh)
+    return root
+
+
 def write_chat_template(root: str, chat_template: str, vocab: int) -> Optional[int]:
     """Makes the tokenizer of the checkpoint directory ``root`` an instruct
     model's: every ``<|...|>`` marker of ``chat_template`` becomes a special
