@@ -326,7 +326,7 @@ class GpuWorkerPool:
                 wit = msg.get("witness") or {}
                 LOG.info("GPU worker %d ready on %s (pid %s, chat template %s, KV cache %s%s)", who.index, who.device,
                          msg.get("pid"), wit.get("chat_template", "n/a"), wit.get("kv_dtype", "n/a"),
-                         f", moe={wit['moe']}" if wit.get("moe") else "")
+                         f", moe={wit['moe']} moe_weights={wit.get('moe_weights', 'bf16')}" if wit.get("moe") else "")
         if not any(w.ready and w.alive for w in self.workers):
             raise RuntimeError("no GPU worker started")
         self._initialised = True
@@ -735,6 +735,8 @@ def _witness(dev: str, model=None) -> dict:
     kv = {"kv_dtype": model.cfg.kv_dtype} if model is not None else {}
     if model is not None and getattr(model.cfg, "n_experts", 0):  # a routed expert MLP: "<experts>x<per token>"
         kv["moe"] = f"{model.cfg.n_experts}x{model.cfg.experts_per_tok}"
+        # the experts' weight format: block-scaled e4m3 (128 x 128 blocks) or bf16
+        kv["moe_weights"] = "fp8b128" if getattr(model.cfg, "moe_weight_dtype", "bf16") == "fp8b" else "bf16"
     if not dev.startswith("cuda"):
         return {"device": dev, **kv}
     try:

@@ -115,6 +115,11 @@ class LMConfig:
     experts_per_tok: int = 0
     moe_intermediate: int = 0
     norm_topk: bool = True
+    # the experts' weight format: "bf16", or "fp8b" -- e4m3 bytes with one fp32
+    # scale per 128 x 128 block (ops.reference.block_fp8_dequant; ops.moe_mlp_w8),
+    # as a block-scaled FP8 checkpoint stores them.  Set by the loader from the
+    # checkpoint; a random-init preset with "fp8b" quantises its random experts
+    moe_weight_dtype: str = "bf16"
 
     @property
     def qkv_dim(self) -> int:
@@ -241,6 +246,93 @@ def _moe_config(hf: dict) -> Tuple[Optional[tuple], Optional[str]]:
                       f"num_experts_per_tok {k} are outside the routed MLP kernels' contract (hidden and "
                       f"intermediate multiples of 64, hidden <= 8192, at most 256 experts)")
     return (ne, k, inter, bool(hf.get("norm_topk_prob", False))), None
+
+
+# Block-scaled FP8 checkpoints (quantization_config.quant_method "fp8"): the
+# projections that may be stored as F8_E4M3 with an F32 ``weight_scale_inv``
+# sibling of shape [ceil(N / 128), ceil(K / 128)].  Everything else -- embeddings,
+# lm_head, norms, biases, the router mlp.gate.weight -- must stay unquantised.
+FP8_BLOCK = 128
+_FP8_PROJ_SUFFIXES = ("self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight",
+                      "self_attn.o_proj.weight", "gate_proj.weight", "up_proj.weight", "down_proj.weight")
+_SCALE_SUFFIX = "_scale_inv"
+
+
+def _fp8_config(hf: dict) -> Tuple[bool, Optional[str]]:
+    """(the checkpoint declares the block-scaled FP8 layout, None), or
+    (False, reason) naming the ``quantization_config`` key that is refused."""
+    qc = hf.get("quantization_config")
+    if qc is None:
+        return False, None
+    if not isinstance(qc, dict):
+        return False, "quantization_config is not an object"
+    method = qc.get("quant_method")
+    if method != "fp8":
+        return False, (f"quantization_config.quant_method {method!r} is not supported (only 'fp8' with "
+                       f"weight_block_size [128, 128])")
+    fmt = qc.get("fmt", "e4m3")
+    if fmt != "e4m3":
+        return False, f"quantization_config.fmt {fmt!r} is not supported (only 'e4m3')"
+    wbs = qc.get("weight_block_size")
+    if wbs is None or list(wbs) != [FP8_BLOCK, FP8_BLOCK]:
+        return False, (f"quantization_config.weight_block_size {wbs!r} is not supported (only [128, 128]: "
+                       f"per-tensor FP8 with weight_scale / input_scale is not loaded)")
+    scheme = qc.get("activation_scheme", "dynamic")
+    if scheme != "dynamic":
+        return False, (f"quantization_config.activation_scheme {scheme!r} is not supported (only 'dynamic': "
+                       f"there are no stored activation scales to apply; activations stay bf16)")
+    return True, None
+
+
+def _checkpoint_headers(path: str) -> Dict[str, tuple]:
+    """name -> (safetensors dtype string, shape) of every tensor (headers only)."""
+    from safetensors import safe_open
+    heads: Dict[str, tuple] = {}
+    for fn in sorted(os.listdir(path)):
+        if fn.endswith(".safetensors"):
+            with safe_open(os.path.join(path, fn), framework="pt") as f:
+                for k in f.keys():
+                    sl = f.get_slice(k)
+                    heads[k] = (str(sl.get_dtype()), tuple(sl.get_shape()))
+    return heads
+
+
+def _fp8_tensor_problem(heads: Dict[str, tuple], fp8: bool) -> Optional[str]:
+    """The first tensor that breaks the block-scaled FP8 layout, decided per
+    tensor from the headers: an F8_E4M3 projection weight needs its F32
+    ``weight_scale_inv`` of the ceil-divided shape, any other weight must
+    have none, and nothing but a projection may be F8."""
+    for n in sorted(heads):
+        dt, shape = heads[n]
+        if n.endswith(".weight" + _SCALE_SUFFIX):
+            base = n[:-len(_SCALE_SUFFIX)]
+            if base not in heads or not heads[base][0].startswith("F8"):
+                return f"tensor {n} has no F8_E4M3 tensor {base} to scale"
+            continue
+        if n.endswith((".weight_scale", ".input_scale")):
+            return (f"tensor {n} is not supported (per-tensor FP8 scales; only the block-scaled layout with "
+                    f"weight_scale_inv is loaded)")
+        if not dt.startswith("F8"):
+            continue
+        if dt != "F8_E4M3":
+            return f"tensor {n} has dtype {dt} (only F8_E4M3 is supported)"
+        if not fp8:
+            return f"tensor {n} is F8_E4M3 but config.json has no quantization_config"
+        if not (n.startswith("model.layers.") and n.endswith(_FP8_PROJ_SUFFIXES)):
+            return (f"tensor {n} must not be F8_E4M3 (only the q/k/v/o, dense-MLP and expert projections may be "
+                    f"quantised)")
+        sn = n + _SCALE_SUFFIX
+        if sn not in heads:
+            return f"tensor {sn} is missing (the scales of the F8_E4M3 tensor {n})"
+        want = tuple(-(-d // FP8_BLOCK) for d in shape)
+        if heads[sn][0] != "F32":
+            return f"tensor {sn} has dtype {heads[sn][0]}, expected F32"
+        if len(shape) != 2 or heads[sn][1] != want:
+            return (f"tensor {sn} has shape {list(heads[sn][1])}, expected {list(want)} (one scale per 128 x 128 "
+                    f"block of {list(shape)})")
+    return None
+
+
 _LAYER_TENSORS = ("input_layernorm.weight", "post_attention_layernorm.weight", "self_attn.q_proj.weight",
                   "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.o_proj.weight",
                   "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
@@ -259,17 +351,6 @@ def _checkpoint_rope(hf: dict) -> Tuple[float, Optional[tuple]]:
     scaling = hf.get("rope_scaling") or params
     theta = hf.get("rope_theta", params.get("rope_theta", 10000.0))
     return float(theta), ops.reference.rope_scaling_key(scaling)
-
-
-def _checkpoint_tensor_names(path: str) -> List[str]:
-    """Tensor names of every *.safetensors file of a directory (headers only)."""
-    from safetensors import safe_open
-    names: List[str] = []
-    for fn in sorted(os.listdir(path)):
-        if fn.endswith(".safetensors"):
-            with safe_open(os.path.join(path, fn), framework="pt") as f:
-                names.extend(f.keys())
-    return names
 
 
 def _checkpoint_tensor_shapes(path: str, suffixes: tuple) -> Dict[str, tuple]:
@@ -373,12 +454,20 @@ def check_checkpoint(path: str, chat_template: Optional[str] = "auto") -> Option
         _checkpoint_rope(hf)
     except (ValueError, TypeError) as e:
         return f"rope_scaling: {e}"
+    fp8, why = _fp8_config(hf)
+    if why is not None:
+        return why
     try:
-        names = _checkpoint_tensor_names(path)
+        heads = _checkpoint_headers(path)
     except Exception as e:  # noqa: BLE001 -- a truncated or foreign file: refuse with its error
         return f"safetensors of {path} cannot be read ({e})"
-    if not names:
+    if not heads:
         return f"{path} holds no *.safetensors file"
+    why = _fp8_tensor_problem(heads, fp8)
+    if why is not None:
+        return why
+    # the scales are consumed with their tensors (checked above)
+    names = [n for n in heads if not n.endswith(".weight" + _SCALE_SUFFIX)]
     layers = hf["num_hidden_layers"]
     consumed = {"model.embed_tokens.weight", "model.norm.weight", "lm_head.weight"}
     required = {"model.embed_tokens.weight", "model.norm.weight"}
@@ -436,6 +525,12 @@ def check_checkpoint(path: str, chat_template: Optional[str] = "auto") -> Option
             exp, keys = next(v for s, v in want.items() if n.endswith(s))
             if shapes[n] != exp:
                 return f"tensor {n} has shape {list(shapes[n])}, expected {list(exp)} ({keys})"
+        # the experts are stored in one format: the stacked device tensors hold one
+        f8 = [n for n in sorted(shapes) if ".mlp.experts." in n and heads[n][0] == "F8_E4M3"]
+        plain = [n for n in sorted(shapes) if ".mlp.experts." in n and heads[n][0] != "F8_E4M3"]
+        if f8 and plain:
+            return (f"tensor {plain[0]} is {heads[plain[0]][0]} but {f8[0]} is F8_E4M3 (the experts must all be "
+                    f"in one format)")
     if "lm_head.weight" not in have and hf.get("tie_word_embeddings") is False:
         return "tensor lm_head.weight is missing and tie_word_embeddings is false"
     if chat_template is not None:
@@ -565,7 +660,12 @@ class LocalLM:
             raise ValueError(f"{cfg.name}: per-head q/k norms need head_dim 64 or 128, got {cfg.head_dim}")
         # routed expert MLP (Qwen3-MoE): w["l{i}.router"] [E, H], w["l{i}.we_gu"] [E, 2I, H] (an expert's gate
         # rows, then its up rows), w["l{i}.we_down"] [E, H, I], all bf16
+        # -- or, moe_weight_dtype "fp8b", w["l{i}.we_gu8"] / w["l{i}.we_down8"] in e4m3 with the block scales
+        # w["l{i}.we_gu_s"] [E, 2 ceil(I / 128), ceil(H / 128)] / w["l{i}.we_down_s"] [E, ceil(H / 128), ceil(I / 128)]
         self.moe = cfg.n_experts > 0
+        if cfg.moe_weight_dtype not in ("bf16", "fp8b"):
+            raise ValueError(f"moe_weight_dtype must be 'bf16' or 'fp8b', got {cfg.moe_weight_dtype!r}")
+        self.moe_w8 = self.moe and cfg.moe_weight_dtype == "fp8b"
         if self.moe:
             if "fp8" in (cfg.prefill_dtype, cfg.decode_dtype):
                 raise ValueError(f"{cfg.name} has a routed expert MLP, which has no MXFP8 GEMM: use "
@@ -582,6 +682,9 @@ class LocalLM:
                                  f"the routed MLP kernels' contract (ops.moe_supported)")
             if "l0.router" not in self.w:
                 raise ValueError(f"{cfg.name}: n_experts {cfg.n_experts} but the weights hold no l0.router")
+            if ("l0.we_gu8" in self.w) != self.moe_w8:
+                raise ValueError(f"{cfg.name}: moe_weight_dtype {cfg.moe_weight_dtype!r} does not match the weights "
+                                 f"({'l0.we_gu8' if 'l0.we_gu8' in self.w else 'l0.we_gu'})")
         self._fold_norms()
         c = cfg
         # the routed MLP's scratch, once, like attn_ws / wgemm_ws: decode steps
@@ -777,8 +880,16 @@ class LocalLM:
             w[f"l{i}.wo"] = rnd(c.hidden, c.n_heads * c.head_dim, std=out_std)
             if c.n_experts:
                 w[f"l{i}.router"] = rnd(c.n_experts, c.hidden)
-                w[f"l{i}.we_gu"] = rnd(c.n_experts, 2 * c.moe_intermediate, c.hidden)
-                w[f"l{i}.we_down"] = rnd(c.n_experts, c.hidden, c.moe_intermediate, std=out_std)
+                gu = rnd(c.n_experts, 2 * c.moe_intermediate, c.hidden)
+                down = rnd(c.n_experts, c.hidden, c.moe_intermediate, std=out_std)
+                if c.moe_weight_dtype == "fp8b":  # the same draws, quantised as a block-scaled checkpoint's are
+                    inter = c.moe_intermediate
+                    g8, gs = ops.block_fp8_quant(gu[:, :inter])
+                    u8, us = ops.block_fp8_quant(gu[:, inter:])
+                    w[f"l{i}.we_gu8"], w[f"l{i}.we_gu_s"] = torch.cat([g8, u8], 1), torch.cat([gs, us], 1)
+                    w[f"l{i}.we_down8"], w[f"l{i}.we_down_s"] = ops.block_fp8_quant(down)
+                    continue
+                w[f"l{i}.we_gu"], w[f"l{i}.we_down"] = gu, down
                 continue
             w[f"l{i}.wgu"] = rnd(2 * c.intermediate, c.hidden)
             w[f"l{i}.wdown"] = rnd(c.hidden, c.intermediate, std=out_std)
@@ -831,7 +942,9 @@ class LocalLM:
         """Loads a Llama-, Qwen2- or Qwen3-format checkpoint directory
         (config.json + *.safetensors) as the model it is: RoPE scaling
         ("linear", "llama3"), q/k/v projection biases and Qwen3's per-head
-        q/k RMSNorm included.  A directory the loader cannot
+        q/k RMSNorm included.  A block-scaled FP8 checkpoint keeps its experts
+        in e4m3 (``moe_weight_dtype`` "fp8b") and has every other F8 projection
+        dequantised to bf16 here.  A directory the loader cannot
         reproduce raises :class:`CheckpointUnsupported` with the reason
         (:func:`check_checkpoint`)."""
         from safetensors.torch import load_file
@@ -852,6 +965,7 @@ class LocalLM:
         if moe is not None:
             cfg = replace(cfg, n_experts=moe[0], experts_per_tok=moe[1], moe_intermediate=moe[2], norm_topk=moe[3])
         cfg = replace(cfg, **cfg_overrides)
+        fp8 = _fp8_config(hf)[0]
         if cfg.prefill_dtype == "auto" and not MXFP8_CHECKPOINT_OK:
             # a real checkpoint keeps bf16 prefill GEMMs unless fp8 is asked
             # for by name: the MXFP8 prefill fails MXFP8_CHECKPOINT_GATE on
@@ -859,8 +973,9 @@ class LocalLM:
             cfg = replace(cfg, prefill_dtype="bf16")
         files = [os.path.join(path, fn) for fn in sorted(os.listdir(path)) if fn.endswith(".safetensors")]
         if moe is not None:
-            # 58 GB of experts at the 30B-A3B geometry: tensors are read one at
-            # a time from the mapped files, never as a second host copy
+            # 58 GB of experts at the 30B-A3B geometry (29 GB block-scaled FP8):
+            # tensors are read one at a time from the mapped files, never as a
+            # second host copy
             raw = _LazyTensors(files)
         else:
             raw = {}
@@ -870,7 +985,15 @@ class LocalLM:
             dev = torch.device(device)
 
             def g(k):
-                return raw[k].to(dtype=torch.bfloat16, device=dev).contiguous()
+                t = raw[k]
+                if t.dtype == torch.float8_e4m3fn:  # an F8 projection outside the experts: bf16 at load
+                    return ops.block_fp8_dequant(t.to(dev), raw[k + _SCALE_SUFFIX].to(dev), torch.bfloat16).contiguous()
+                return t.to(dtype=torch.bfloat16, device=dev).contiguous()
+
+            experts_f8 = (moe is not None and fp8
+                          and raw["model.layers.0.mlp.experts.0.gate_proj.weight"].dtype == torch.float8_e4m3fn)
+            if experts_f8:
+                cfg = replace(cfg, moe_weight_dtype="fp8b")
 
             w = {"embed": g("model.embed_tokens.weight"), "norm_f": g("model.norm.weight"),
                  "lm_head": g("lm_head.weight") if "lm_head.weight" in raw else g("model.embed_tokens.weight")}
@@ -890,14 +1013,27 @@ class LocalLM:
                 if moe is not None:
                     E, _, inter, _ = moe
                     w[f"l{i}.router"] = g(p + "mlp.gate.weight")
-                    gu = torch.empty((E, 2 * inter, cfg.hidden), dtype=torch.bfloat16, device=dev)
-                    down = torch.empty((E, cfg.hidden, inter), dtype=torch.bfloat16, device=dev)
+                    wdt = torch.float8_e4m3fn if experts_f8 else torch.bfloat16
+                    gu = torch.empty((E, 2 * inter, cfg.hidden), dtype=wdt, device=dev)
+                    down = torch.empty((E, cfg.hidden, inter), dtype=wdt, device=dev)
+                    if experts_f8:  # the e4m3 bytes as they are, and their block scales beside them
+                        nbi, nbh = -(-inter // FP8_BLOCK), -(-cfg.hidden // FP8_BLOCK)
+                        gu_s = torch.empty((E, 2 * nbi, nbh), dtype=torch.float32, device=dev)
+                        down_s = torch.empty((E, nbh, nbi), dtype=torch.float32, device=dev)
                     for e in range(E):  # straight into the stacked device tensors, one expert at a time
                         q = f"{p}mlp.experts.{e}."
                         gu[e, :inter].copy_(raw[q + "gate_proj.weight"])
                         gu[e, inter:].copy_(raw[q + "up_proj.weight"])
                         down[e].copy_(raw[q + "down_proj.weight"])
-                    w[f"l{i}.we_gu"], w[f"l{i}.we_down"] = gu, down
+                        if experts_f8:
+                            gu_s[e, :nbi].copy_(raw[q + "gate_proj.weight" + _SCALE_SUFFIX])
+                            gu_s[e, nbi:].copy_(raw[q + "up_proj.weight" + _SCALE_SUFFIX])
+                            down_s[e].copy_(raw[q + "down_proj.weight" + _SCALE_SUFFIX])
+                    if experts_f8:
+                        w[f"l{i}.we_gu8"], w[f"l{i}.we_gu_s"] = gu, gu_s
+                        w[f"l{i}.we_down8"], w[f"l{i}.we_down_s"] = down, down_s
+                    else:
+                        w[f"l{i}.we_gu"], w[f"l{i}.we_down"] = gu, down
                     continue
                 w[f"l{i}.wgu"] = torch.cat([g(p + "mlp.gate_proj.weight"), g(p + "mlp.up_proj.weight")], 0).contiguous()
                 w[f"l{i}.wdown"] = g(p + "mlp.down_proj.weight")
@@ -932,16 +1068,22 @@ class LocalLM:
         returned (the add_rmsnorm that follows a dense MLP, fused into the
         combine).  More rows than the workspace holds go in chunks."""
         c = self.cfg
-        args = (self.w[f"l{i}.router"], self.w[f"l{i}.we_gu"], self.w[f"l{i}.we_down"], c.experts_per_tok,
-                c.norm_topk)
+        w = self.w
+        if self.moe_w8:  # block-scaled e4m3 experts: the same launches over half the weight bytes
+            op = ops.moe_mlp_w8
+            args = (w[f"l{i}.router"], w[f"l{i}.we_gu8"], w[f"l{i}.we_gu_s"], w[f"l{i}.we_down8"],
+                    w[f"l{i}.we_down_s"], c.experts_per_tok, c.norm_topk)
+        else:
+            op = ops.moe_mlp
+            args = (w[f"l{i}.router"], w[f"l{i}.we_gu"], w[f"l{i}.we_down"], c.experts_per_tok, c.norm_topk)
         T = h.shape[0]
         if T <= self.moe_rows:
-            return ops.moe_mlp(h, *args, residual=resid, norm_w=nxt, eps=c.eps, workspace=self.moe_ws)
+            return op(h, *args, residual=resid, norm_w=nxt, eps=c.eps, workspace=self.moe_ws)
         out = torch.empty_like(h) if nxt is not None else None
         for a in range(0, T, self.moe_rows):
             b = min(T, a + self.moe_rows)
-            ops.moe_mlp(h[a:b], *args, residual=resid[a:b], norm_w=nxt, eps=c.eps, workspace=self.moe_ws,
-                        out=None if out is None else out[a:b])
+            op(h[a:b], *args, residual=resid[a:b], norm_w=nxt, eps=c.eps, workspace=self.moe_ws,
+               out=None if out is None else out[a:b])
         return resid if out is None else out
 
     def _mlp_norm(self, i: int, h: torch.Tensor, resid: torch.Tensor, nxt: torch.Tensor) -> torch.Tensor:
@@ -1543,7 +1685,7 @@ class LocalLM:
         """fp32 logits [T, vocab] of ``tokens`` at positions [start_pos, start_pos + T)."""
         c = self.cfg
         dev = self.device
-        w = {k: v.float() for k, v in self.w.items()}
+        w = {k: v.float() for k, v in self.w.items() if v.dtype != torch.float8_e4m3fn}
         ids = torch.tensor(list(tokens), dtype=torch.long, device=dev)
         T = ids.numel()
         x = w["embed"][ids]
@@ -1575,8 +1717,13 @@ class LocalLM:
             x = x + o @ w[f"l{i}.wo"].t()
             h = rms(x, w[f"l{i}.ln2"])
             if self.moe:
-                x = x + ops.reference.moe_mlp_math(h, w[f"l{i}.router"], w[f"l{i}.we_gu"], w[f"l{i}.we_down"],
-                                                   c.experts_per_tok, c.norm_topk)
+                if self.moe_w8:  # the experts dequantised exactly (fp32), one layer at a time
+                    we_gu, we_down = ops.reference.moe_w8_dequant(self.w[f"l{i}.we_gu8"], self.w[f"l{i}.we_gu_s"],
+                                                                  self.w[f"l{i}.we_down8"], self.w[f"l{i}.we_down_s"])
+                else:
+                    we_gu, we_down = w[f"l{i}.we_gu"], w[f"l{i}.we_down"]
+                x = x + ops.reference.moe_mlp_math(h, w[f"l{i}.router"], we_gu, we_down, c.experts_per_tok,
+                                                   c.norm_topk)
                 continue
             gu = h @ w[f"l{i}.wgu"].t()
             g_, u_ = gu[:, :c.intermediate], gu[:, c.intermediate:]

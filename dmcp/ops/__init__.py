@@ -23,6 +23,7 @@ from .hip import (TGEMM_MAX_ROWS, tgemm, tgemm_lm_head_argmax, tgemm_lm_head_sam
 from .hip import MOE_MAX_PAIRS, moe_supported, moe_workspace  # noqa: F401
 from .reference import Penalty, penalize  # noqa: F401
 from .reference import SharedPrefix, mx_dequant, quantize_weight, rope_tables, weight_dequant  # noqa: F401
+from .reference import block_fp8_dequant, block_fp8_quant  # noqa: F401
 
 
 def _on(t):
@@ -60,8 +61,9 @@ DEVICE_OPS = ("history_mark", "history_reset",
               "decode_embed_norm",
               "mx_quant", "rmsnorm_mx", "pgemm", "pgemm_resid", "pgemm_swiglu", "pgemm_qkv", "fused_rope_kv",
               "wgemm_rope_kv", "tgemm_rope_kv",
-              # the routed expert MLP of a mixture-of-experts layer (csrc/moe.hip)
-              "moe_route", "moe_mlp")
+              # the routed expert MLP of a mixture-of-experts layer (csrc/moe.hip), over bf16 and over
+              # block-scaled FP8 expert weights
+              "moe_route", "moe_mlp", "moe_mlp_w8")
 for _name in DEVICE_OPS:
     globals()[_name] = _by_device(_name)
 del _name

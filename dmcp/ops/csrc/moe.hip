@@ -32,9 +32,21 @@
 // Blocks past the live tile count (a device value) exit at once.  No atomics
 // of any kind: every output element has one writer and a fixed summation
 // order, so equal inputs give equal bits.
+//
+// Block-scaled FP8 expert weights (dmcp_moe_mlp_w8; the format is defined in
+// dmcp/ops/reference.py, block_fp8_dequant): e4m3 bytes with one fp32
+// multiplier per 128 x 128 block.  Steps 4 and 5 then run the same kernel body
+// with WT = uint8_t: a lane takes 16 weight bytes per 64-deep chunk, widens
+// them exactly to bf16 in registers (fp8x8_to_bf16x8) and feeds the same MFMA;
+// the products of a 128-deep K block go to a partial accumulator and the
+// block's scale is applied to that fp32 partial sum (acc += s * part), never
+// to a weight.  Everything else -- activations, routing, grouping, combine --
+// is bf16 / fp32 as above.
 #include "dmcp_common.hpp"
 
 namespace {
+
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr int kMaxExperts = 256;
 constexpr int kEPL = kMaxExperts / kWave;  // expert slots per lane of the routing wave
@@ -200,13 +212,32 @@ __global__ __launch_bounds__(kWave) void moe_scatter_kernel(const int32_t* __res
 // chunks, [row][8 x 16 B] with chunk j of row r in slot j ^ (r & 7)
 // (conflict-free ds_read_b128 of the B operand), double buffered: chunk c + 1
 // is loaded to registers before chunk c's MFMAs and stored after them.
-template <int RT, bool SWIGLU>
+//
+// WT = uint16_t: bf16 weights, ws unused.  WT = uint8_t: e4m3 weights with the
+// block scales ws (gate/up: [E][2 ceil(N / 128)][ceil(K / 128)], the gate's
+// block rows, then the up's; down: [E][ceil(N / 128)][ceil(K / 128)]).  A
+// block's 64 gate + 64 up columns, or its 128 down columns, lie inside one
+// 128-row scale block, so per 128-deep K block the wave needs one scalar per
+// fragment (gate and up differ; down's two fragments share one).  A lane
+// takes the 16 bytes k = 16 g .. 16 g + 15 of each 64-deep chunk in one load
+// (two chunks per K block; one when K % 128 == 64 ends on a half block) and
+// uses 8 of them per MFMA: even g the low half first, odd g the high half
+// first, i.e. sub-step kk pairs with the X piece 2 g + (kk ^ (g & 1)).  K is
+// permuted inside the chunk, for A and B alike.  The parity flip keeps the
+// ds_read_b128 of X conflict-free: in each of the instruction's 16-lane groups
+// (eight rows of one g, eight of the next) the two g read pieces of opposite
+// parity, which the slot swizzle j ^ (r & 7) sends to disjoint slots of the
+// 256-byte bank row, as the bf16 mapping's pieces 4 kk + g and 4 kk + g + 1 are.
+template <int RT, bool SWIGLU, typename WT>
 __global__ __launch_bounds__(kBlock) void moe_gemm_kernel(const uint16_t* __restrict__ x,
-                                                          const uint16_t* __restrict__ w,
+                                                          const WT* __restrict__ w,
+                                                          const float* __restrict__ ws,
                                                           const int32_t* __restrict__ perm,
                                                           const int32_t* __restrict__ tiles,
                                                           const int32_t* __restrict__ ntiles, uint16_t* __restrict__ act,
                                                           float* __restrict__ y, int P, int K, int N, int topk) {
+    constexpr bool W8 = sizeof(WT) == 1;
+    constexpr int LK = W8 ? 16 : 8;  // weight elements of a lane's 16-byte load
     constexpr int MT = RT * 16;
     constexpr int XP = MT * 8 / kBlock > 0 ? MT * 8 / kBlock : 1;  // 16-B pieces per thread per chunk
     static_assert(MT * 8 % kBlock == 0 || MT * 8 < kBlock, "row tile");
@@ -235,9 +266,9 @@ __global__ __launch_bounds__(kBlock) void moe_gemm_kernel(const uint16_t* __rest
     const int c1 = SWIGLU ? c0 : c0 + 64;          // output column of fragment 1
     const bool f1 = SWIGLU || c1 < N;              // fragment 1 exists (H % 128 == 64: the last block's does not)
     const size_t wrows = SWIGLU ? 2 * (size_t)N : (size_t)N;
-    const uint16_t* wbase = w + (size_t)e * wrows * K;
-    const uint16_t* wa0 = wbase + (size_t)(c0 + l16) * K + g * 8;
-    const uint16_t* wa1 = wbase + (size_t)(SWIGLU ? N + c0 + l16 : (f1 ? c1 + l16 : c0 + l16)) * K + g * 8;
+    const WT* wbase = w + (size_t)e * wrows * K;
+    const WT* wa0 = wbase + (size_t)(c0 + l16) * K + g * LK;
+    const WT* wa1 = wbase + (size_t)(SWIGLU ? N + c0 + l16 : (f1 ? c1 + l16 : c0 + l16)) * K + g * LK;
 
     const uint16_t* xsrc[XP];
     int xdst[XP];
@@ -262,49 +293,135 @@ __global__ __launch_bounds__(kBlock) void moe_gemm_kernel(const uint16_t* __rest
 #pragma unroll
     for (int i = 0; i < XP; ++i)
         if (xon[i]) lds[xdst[i]] = *reinterpret_cast<const uint4*>(xsrc[i]);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-        a[0][kk] = *reinterpret_cast<const uint4*>(wa0 + kk * 32);
-        a[1][kk] = *reinterpret_cast<const uint4*>(wa1 + kk * 32);
-    }
-    __syncthreads();
-    for (int c = 0; c < chunks; ++c) {
-        const bool more = c + 1 < chunks;
-        if (more) {
-#pragma unroll
-            for (int i = 0; i < XP; ++i)
-                if (xon[i]) xr[i] = *reinterpret_cast<const uint4*>(xsrc[i] + (c + 1) * 64);
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                an[0][kk] = *reinterpret_cast<const uint4*>(wa0 + (c + 1) * 64 + kk * 32);
-                an[1][kk] = *reinterpret_cast<const uint4*>(wa1 + (c + 1) * 64 + kk * 32);
-            }
-        }
-        const uint4* xl = lds + (c & 1) * (MT * 8);
+    if constexpr (!W8) {
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
-#pragma unroll
-            for (int t = 0; t < RT; ++t) {
-                const int r = 16 * t + l16;
-                const bf16x8_t b = as_bf16x8(xl[r * 8 + ((4 * kk + g) ^ (r & 7))]);
-                acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(a[0][kk]), b, acc[0][t], 0, 0, 0);
-                acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(a[1][kk]), b, acc[1][t], 0, 0, 0);
-            }
+            a[0][kk] = *reinterpret_cast<const uint4*>(wa0 + kk * 32);
+            a[1][kk] = *reinterpret_cast<const uint4*>(wa1 + kk * 32);
         }
-        if (more) {
-            uint4* xs = lds + ((c + 1) & 1) * (MT * 8);
+        __syncthreads();
+        for (int c = 0; c < chunks; ++c) {
+            const bool more = c + 1 < chunks;
+            if (more) {
 #pragma unroll
-            for (int i = 0; i < XP; ++i)
-                if (xon[i]) xs[xdst[i]] = xr[i];
+                for (int i = 0; i < XP; ++i)
+                    if (xon[i]) xr[i] = *reinterpret_cast<const uint4*>(xsrc[i] + (c + 1) * 64);
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) {
+                    an[0][kk] = *reinterpret_cast<const uint4*>(wa0 + (c + 1) * 64 + kk * 32);
+                    an[1][kk] = *reinterpret_cast<const uint4*>(wa1 + (c + 1) * 64 + kk * 32);
+                }
+            }
+            const uint4* xl = lds + (c & 1) * (MT * 8);
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
-                a[0][kk] = an[0][kk];
-                a[1][kk] = an[1][kk];
+#pragma unroll
+                for (int t = 0; t < RT; ++t) {
+                    const int r = 16 * t + l16;
+                    const bf16x8_t b = as_bf16x8(xl[r * 8 + ((4 * kk + g) ^ (r & 7))]);
+                    acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(a[0][kk]), b, acc[0][t], 0, 0, 0);
+                    acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(a[1][kk]), b, acc[1][t], 0, 0, 0);
+                }
+            }
+            if (more) {
+                uint4* xs = lds + ((c + 1) & 1) * (MT * 8);
+#pragma unroll
+                for (int i = 0; i < XP; ++i)
+                    if (xon[i]) xs[xdst[i]] = xr[i];
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) {
+                    a[0][kk] = an[0][kk];
+                    a[1][kk] = an[1][kk];
+                }
+            }
+            // one barrier per chunk: chunk c + 1 is complete, and nobody still
+            // reads the buffer that chunk c + 2 will overwrite after the next one
+            __syncthreads();
+        }
+    } else {
+        // a[f][hh]: fragment f's 16 bytes of chunk 2 kb + hh.  The K block after
+        // this one is in flight while this one multiplies: as many bytes per
+        // wave as the bf16 form keeps in flight, over twice the depth.
+        const int nkb = (chunks + 1) >> 1;
+        const int nbn = (N + 127) >> 7;
+        const float* sc0 = ws + ((size_t)e * (SWIGLU ? 2 * nbn : nbn) + (SWIGLU ? blockIdx.x >> 1 : blockIdx.x)) * nkb;
+        const float* sc1 = SWIGLU ? sc0 + (size_t)nbn * nkb : sc0;
+        const bool odd = g & 1;
+        u32x4_t xq[XP];  // chunk c + 1 of X on its way to LDS (a native vector: the array stays in registers)
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+            const int cc = min(hh, chunks - 1);  // half a block: its second slot repeats the first, unused
+            a[0][hh] = *reinterpret_cast<const uint4*>(wa0 + cc * 64);
+            a[1][hh] = *reinterpret_cast<const uint4*>(wa1 + cc * 64);
+        }
+        __syncthreads();
+        for (int kb = 0; kb < nkb; ++kb) {
+            const bool next = kb + 1 < nkb;
+            if (next) {
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh) {
+                    const int cc = min(2 * kb + 2 + hh, chunks - 1);
+                    an[0][hh] = *reinterpret_cast<const uint4*>(wa0 + cc * 64);
+                    an[1][hh] = *reinterpret_cast<const uint4*>(wa1 + cc * 64);
+                }
+            }
+            const float s0 = sc0[kb], s1 = sc1[kb];
+            f32x4_t part[2][RT];
+#pragma unroll
+            for (int f = 0; f < 2; ++f)
+#pragma unroll
+                for (int t = 0; t < RT; ++t) part[f][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh) {
+                const int c = 2 * kb + hh;
+                if (c >= chunks) break;  // uniform: K % 128 == 64, the last block is one chunk
+                const bool more = c + 1 < chunks;
+                if (more) {
+#pragma unroll
+                    for (int i = 0; i < XP; ++i)
+                        if (xon[i]) xq[i] = *reinterpret_cast<const u32x4_t*>(xsrc[i] + (c + 1) * 64);
+                }
+                const uint4* xl = lds + (c & 1) * (MT * 8);
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) {
+                    const bool hi = (kk == 1) != odd;
+                    const uint4 w0 = fp8x8_to_bf16x8(hi ? make_uint2(a[0][hh].z, a[0][hh].w)
+                                                        : make_uint2(a[0][hh].x, a[0][hh].y));
+                    const uint4 w1 = fp8x8_to_bf16x8(hi ? make_uint2(a[1][hh].z, a[1][hh].w)
+                                                        : make_uint2(a[1][hh].x, a[1][hh].y));
+                    const int j = 2 * g + (kk ^ (g & 1));
+#pragma unroll
+                    for (int t = 0; t < RT; ++t) {
+                        const int r = 16 * t + l16;
+                        const bf16x8_t b = as_bf16x8(xl[r * 8 + (j ^ (r & 7))]);
+                        part[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w0), b, part[0][t], 0, 0, 0);
+                        part[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w1), b, part[1][t], 0, 0, 0);
+                    }
+                }
+                if (more) {
+                    u32x4_t* xs = reinterpret_cast<u32x4_t*>(lds + ((c + 1) & 1) * (MT * 8));
+#pragma unroll
+                    for (int i = 0; i < XP; ++i)
+                        if (xon[i]) xs[xdst[i]] = xq[i];
+                }
+                __syncthreads();  // as in the bf16 loop: one barrier per chunk
+            }
+#pragma unroll
+            for (int t = 0; t < RT; ++t) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    acc[0][t][i] = fmaf(s0, part[0][t][i], acc[0][t][i]);
+                    acc[1][t][i] = fmaf(s1, part[1][t][i], acc[1][t][i]);
+                }
+            }
+            if (next) {
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh) {
+                    a[0][hh] = an[0][hh];
+                    a[1][hh] = an[1][hh];
+                }
             }
         }
-        // one barrier per chunk: chunk c + 1 is complete, and nobody still
-        // reads the buffer that chunk c + 2 will overwrite after the next one
-        __syncthreads();
     }
 
     // lane (l16, g) holds Y[tile row 16 t + l16][fragment column 4 g + i]
@@ -407,14 +524,54 @@ bool moe_shape_ok(int T, int H, int I, int E, int k, int MT) {
            k >= 1 && k <= E && (MT == 32 || MT == 128) && (long long)T * k < (1ll << 30);
 }
 
-template <int RT>
-void launch_gemms(const uint16_t* h, const uint16_t* wgu, const uint16_t* wdown, const int32_t* perm,
-                  const int32_t* tiles, const int32_t* ntiles, uint16_t* act, float* y, int P, int H, int I, int k,
-                  int max_tiles, hipStream_t st) {
-    moe_gemm_kernel<RT, true><<<dim3(I / 64, max_tiles), kBlock, 0, st>>>(h, wgu, perm, tiles, ntiles, act, nullptr,
-                                                                           P, H, I, k);
-    moe_gemm_kernel<RT, false><<<dim3((H + 127) / 128, max_tiles), kBlock, 0, st>>>(act, wdown, perm, tiles, ntiles,
-                                                                                     nullptr, y, P, I, H, k);
+template <int RT, typename WT>
+void launch_gemms(const uint16_t* h, const WT* wgu, const float* sgu, const WT* wdown, const float* sdown,
+                  const int32_t* perm, const int32_t* tiles, const int32_t* ntiles, uint16_t* act, float* y, int P,
+                  int H, int I, int k, int max_tiles, hipStream_t st) {
+    moe_gemm_kernel<RT, true, WT><<<dim3(I / 64, max_tiles), kBlock, 0, st>>>(h, wgu, sgu, perm, tiles, ntiles, act,
+                                                                               nullptr, P, H, I, k);
+    moe_gemm_kernel<RT, false, WT><<<dim3((H + 127) / 128, max_tiles), kBlock, 0, st>>>(
+        act, wdown, sdown, perm, tiles, ntiles, nullptr, y, P, I, H, k);
+}
+
+// The six launches of dmcp_moe_mlp / dmcp_moe_mlp_w8 (WT: the expert weights'
+// element; sgu / sdown: the e4m3 form's block scales, null for bf16).
+template <typename WT>
+int moe_mlp_launch(const void* h, const void* wr, const void* wgu, const void* sgu, const void* wdown,
+                   const void* sdown, void* ids, void* p, void* cnt, void* offs, void* perm, void* tiles, void* ntiles,
+                   void* act, void* y, void* residual, const void* norm_w, void* out, int T, int H, int I, int E, int k,
+                   int norm, int MT, float eps, void* stream) {
+    if (!moe_shape_ok(T, H, I, E, k, MT)) return (int)hipErrorInvalidValue;
+    if (!norm_w && !residual && !out) return (int)hipErrorInvalidValue;
+    if (norm_w && !out) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const int P = T * k;
+    const int max_tiles = (P + MT - 1) / MT + E;
+    if (max_tiles > 65535) return (int)hipErrorInvalidValue;  // grid.y
+    const int wpb = kBlock / kWave;
+    moe_route_kernel<<<(T + wpb - 1) / wpb, kBlock, 0, st>>>((const uint16_t*)h, (const uint16_t*)wr, (int32_t*)ids,
+                                                             (float*)p, T, H, E, k, norm);
+    moe_count_kernel<<<E, kWave, 0, st>>>((const int32_t*)ids, (int32_t*)cnt, P);
+    moe_scatter_kernel<<<E, kWave, 0, st>>>((const int32_t*)ids, (const int32_t*)cnt, (int32_t*)offs, (int32_t*)perm,
+                                            (int32_t*)tiles, (int32_t*)ntiles, P, E, MT, max_tiles);
+    if (MT == 32)
+        launch_gemms<2, WT>((const uint16_t*)h, (const WT*)wgu, (const float*)sgu, (const WT*)wdown,
+                            (const float*)sdown, (const int32_t*)perm, (const int32_t*)tiles, (const int32_t*)ntiles,
+                            (uint16_t*)act, (float*)y, P, H, I, k, max_tiles, st);
+    else
+        launch_gemms<8, WT>((const uint16_t*)h, (const WT*)wgu, (const float*)sgu, (const WT*)wdown,
+                            (const float*)sdown, (const int32_t*)perm, (const int32_t*)tiles, (const int32_t*)ntiles,
+                            (uint16_t*)act, (float*)y, P, H, I, k, max_tiles, st);
+    const int vpt = (H / 8 + kBlock - 1) / kBlock;
+    const float* yy = (const float*)y;
+    const float* pp = (const float*)p;
+    uint16_t* rr = (uint16_t*)residual;
+    const uint16_t* ww = (const uint16_t*)norm_w;
+    uint16_t* oo = (uint16_t*)out;
+    if (vpt == 1) moe_combine_kernel<1><<<T, kBlock, 0, st>>>(yy, pp, rr, ww, oo, H, k, eps);
+    else if (vpt == 2) moe_combine_kernel<2><<<T, kBlock, 0, st>>>(yy, pp, rr, ww, oo, H, k, eps);
+    else moe_combine_kernel<4><<<T, kBlock, 0, st>>>(yy, pp, rr, ww, oo, H, k, eps);
+    return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -440,37 +597,22 @@ int dmcp_moe_mlp(const void* h, const void* wr, const void* wgu, const void* wdo
                  void* offs, void* perm, void* tiles, void* ntiles, void* act, void* y, void* residual,
                  const void* norm_w, void* out, int T, int H, int I, int E, int k, int norm, int MT, float eps,
                  void* stream) {
-    if (!moe_shape_ok(T, H, I, E, k, MT)) return (int)hipErrorInvalidValue;
-    if (!norm_w && !residual && !out) return (int)hipErrorInvalidValue;
-    if (norm_w && !out) return (int)hipErrorInvalidValue;
-    hipStream_t st = (hipStream_t)stream;
-    const int P = T * k;
-    const int max_tiles = (P + MT - 1) / MT + E;
-    if (max_tiles > 65535) return (int)hipErrorInvalidValue;  // grid.y
-    const int wpb = kBlock / kWave;
-    moe_route_kernel<<<(T + wpb - 1) / wpb, kBlock, 0, st>>>((const uint16_t*)h, (const uint16_t*)wr, (int32_t*)ids,
-                                                             (float*)p, T, H, E, k, norm);
-    moe_count_kernel<<<E, kWave, 0, st>>>((const int32_t*)ids, (int32_t*)cnt, P);
-    moe_scatter_kernel<<<E, kWave, 0, st>>>((const int32_t*)ids, (const int32_t*)cnt, (int32_t*)offs, (int32_t*)perm,
-                                            (int32_t*)tiles, (int32_t*)ntiles, P, E, MT, max_tiles);
-    if (MT == 32)
-        launch_gemms<2>((const uint16_t*)h, (const uint16_t*)wgu, (const uint16_t*)wdown, (const int32_t*)perm,
-                        (const int32_t*)tiles, (const int32_t*)ntiles, (uint16_t*)act, (float*)y, P, H, I, k,
-                        max_tiles, st);
-    else
-        launch_gemms<8>((const uint16_t*)h, (const uint16_t*)wgu, (const uint16_t*)wdown, (const int32_t*)perm,
-                        (const int32_t*)tiles, (const int32_t*)ntiles, (uint16_t*)act, (float*)y, P, H, I, k,
-                        max_tiles, st);
-    const int vpt = (H / 8 + kBlock - 1) / kBlock;
-    const float* yy = (const float*)y;
-    const float* pp = (const float*)p;
-    uint16_t* rr = (uint16_t*)residual;
-    const uint16_t* ww = (const uint16_t*)norm_w;
-    uint16_t* oo = (uint16_t*)out;
-    if (vpt == 1) moe_combine_kernel<1><<<T, kBlock, 0, st>>>(yy, pp, rr, ww, oo, H, k, eps);
-    else if (vpt == 2) moe_combine_kernel<2><<<T, kBlock, 0, st>>>(yy, pp, rr, ww, oo, H, k, eps);
-    else moe_combine_kernel<4><<<T, kBlock, 0, st>>>(yy, pp, rr, ww, oo, H, k, eps);
-    return (int)hipGetLastError();
+    return moe_mlp_launch<uint16_t>(h, wr, wgu, nullptr, wdown, nullptr, ids, p, cnt, offs, perm, tiles, ntiles, act,
+                                    y, residual, norm_w, out, T, H, I, E, k, norm, MT, eps, stream);
+}
+
+// The same block over block-scaled FP8 expert weights: wgu8 [E, 2 I, H] and
+// wdown8 [E, H, I] e4m3 bytes, sgu fp32 [E, 2 ceil(I / 128), ceil(H / 128)]
+// (gate block rows, then up block rows) and sdown fp32 [E, ceil(H / 128),
+// ceil(I / 128)]: W[n, k] = e4m3[n, k] * s[n / 128, k / 128].  The other
+// arguments, the workspace parts and the refusals are dmcp_moe_mlp's.
+int dmcp_moe_mlp_w8(const void* h, const void* wr, const void* wgu8, const void* sgu, const void* wdown8,
+                    const void* sdown, void* ids, void* p, void* cnt, void* offs, void* perm, void* tiles,
+                    void* ntiles, void* act, void* y, void* residual, const void* norm_w, void* out, int T, int H,
+                    int I, int E, int k, int norm, int MT, float eps, void* stream) {
+    if (!wgu8 || !sgu || !wdown8 || !sdown) return (int)hipErrorInvalidValue;
+    return moe_mlp_launch<uint8_t>(h, wr, wgu8, sgu, wdown8, sdown, ids, p, cnt, offs, perm, tiles, ntiles, act, y,
+                                   residual, norm_w, out, T, H, I, E, k, norm, MT, eps, stream);
 }
 
 }  // extern "C"

@@ -138,6 +138,8 @@ def lib() -> ctypes.CDLL:
             # h, router, w_gu, w_down, 9 workspace parts (ids, p, cnt, offs, perm, tiles, ntiles, act, y),
             # residual, norm_w, out, T, H, I, E, k, norm_topk, row tile, eps
             "dmcp_moe_mlp": ([_vp] * 16 + [_i, _i, _i, _i, _i, _i, _i, _f, _vp], _i),
+            # the same over block-scaled e4m3 experts: h, router, w_gu8, s_gu, w_down8, s_down, then as above
+            "dmcp_moe_mlp_w8": ([_vp] * 18 + [_i, _i, _i, _i, _i, _i, _i, _f, _vp], _i),
         }
         for name, (args, res) in sigs.items():
             try:
@@ -2086,32 +2088,94 @@ def moe_mlp(h: torch.Tensor, w_router: torch.Tensor, w_gu: torch.Tensor, w_down:
     ``workspace``: :func:`moe_workspace` for at least T rows (allocated per
     call when None; a model passes its own)."""
     T, H, inter, E = _moe_args(h, w_router, w_gu, w_down, top_k, "moe_mlp")
+    return _moe_run("moe_mlp", h, w_router, (w_gu, w_down), T, H, inter, E, top_k, norm_topk, residual, norm_w, eps,
+                    workspace, out)
+
+
+def _moe_run(name, h, w_router, weights, T, H, inter, E, top_k, norm_topk, residual, norm_w, eps, workspace, out):
+    """The checks on workspace, residual, norm and out shared by :func:`moe_mlp`
+    and :func:`moe_mlp_w8`, all before the launch; ``weights``: the tensors
+    between the router and the workspace parts of ``dmcp_<name>``."""
     offs, need = _moe_layout(max(T, 1), H, inter, E, top_k)
     if workspace is None:
         workspace = torch.empty(need, dtype=torch.uint8, device=h.device)
-    _req(workspace, torch.uint8, "moe_mlp.workspace")
+    _req(workspace, torch.uint8, f"{name}.workspace")
     if workspace.numel() < need or workspace.device != h.device:
-        raise HipOpsError(f"moe_mlp: workspace holds {workspace.numel()} bytes on {workspace.device}, "
+        raise HipOpsError(f"{name}: workspace holds {workspace.numel()} bytes on {workspace.device}, "
                           f"{T} rows need {need} on {h.device}")
     if residual is not None:
-        _req(residual, torch.bfloat16, "moe_mlp.residual")
+        _req(residual, torch.bfloat16, f"{name}.residual")
         if residual.shape != h.shape:
-            raise HipOpsError("moe_mlp: residual shape mismatch")
+            raise HipOpsError(f"{name}: residual shape mismatch")
     if norm_w is not None:
-        _req(norm_w, torch.bfloat16, "moe_mlp.norm_w")
+        _req(norm_w, torch.bfloat16, f"{name}.norm_w")
         if norm_w.numel() != H:
-            raise HipOpsError(f"moe_mlp: norm_w holds {norm_w.numel()} elements, a row has {H}")
+            raise HipOpsError(f"{name}: norm_w holds {norm_w.numel()} elements, a row has {H}")
     if norm_w is not None or residual is None:
         out = torch.empty_like(h) if out is None else out
-        _req_out(out, torch.bfloat16, T * H, "moe_mlp.out")
+        _req_out(out, torch.bfloat16, T * H, f"{name}.out")
     else:
         out = None  # residual += m: nothing else is written
     if T:
         base = workspace.data_ptr()
         if base % 16:
-            raise HipOpsError("moe_mlp: workspace must be 16-byte aligned")
+            raise HipOpsError(f"{name}: workspace must be 16-byte aligned")
         parts = [ctypes.c_void_p(base + o) for o in offs]
-        _check(lib().dmcp_moe_mlp(_ptr(h), _ptr(w_router), _ptr(w_gu), _ptr(w_down), *parts, _ptr(residual),
-                                  _ptr(norm_w), _ptr(out), T, H, inter, E, top_k, int(bool(norm_topk)),
-                                  moe_row_tile(T, E, top_k), float(eps), _stream()), "dmcp_moe_mlp")
+        _check(getattr(lib(), f"dmcp_{name}")(_ptr(h), _ptr(w_router), *[_ptr(t) for t in weights], *parts,
+                                              _ptr(residual), _ptr(norm_w), _ptr(out), T, H, inter, E, top_k,
+                                              int(bool(norm_topk)), moe_row_tile(T, E, top_k), float(eps),
+                                              _stream()), f"dmcp_{name}")
     return out if out is not None else residual
+
+
+MOE_W8_BLOCK = 128  # rows and columns of one scale block (dmcp.ops.reference.block_fp8_dequant)
+
+
+def moe_mlp_w8(h: torch.Tensor, w_router: torch.Tensor, w_gu8: torch.Tensor, s_gu: torch.Tensor,
+               w_down8: torch.Tensor, s_down: torch.Tensor, top_k: int, norm_topk: bool,
+               residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0,
+               workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`moe_mlp` over block-scaled FP8 expert weights
+    (dmcp.ops.reference.moe_mlp_w8 defines the format): ``w_gu8`` [E, 2I, H] and
+    ``w_down8`` [E, H, I] in ``torch.float8_e4m3fn`` (a ``uint8`` view is
+    refused), ``s_gu`` fp32 [E, 2 ceil(I / 128), ceil(H / 128)] (gate block
+    rows, then up block rows) and ``s_down`` fp32 [E, ceil(H / 128),
+    ceil(I / 128)].  The grouped GEMMs widen the bytes exactly to bf16 in
+    registers and apply a block's scale to its fp32 partial sum; activations,
+    routing, combine, workspace and launches are :func:`moe_mlp`'s."""
+    name = "moe_mlp_w8"
+    _req(h, torch.bfloat16, f"{name}.h")
+    _req(w_router, torch.bfloat16, f"{name}.w_router")
+    if h.dim() != 2 or w_router.dim() != 2 or h.shape[1] != w_router.shape[1]:
+        raise HipOpsError(f"{name}: h {tuple(h.shape)} does not match the router {tuple(w_router.shape)}")
+    T, H = h.shape
+    E = w_router.shape[0]
+    for t, which in ((w_gu8, "w_gu8"), (w_down8, "w_down8")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float8_e4m3fn:
+            raise HipOpsError(f"{name}.{which}: expected torch.float8_e4m3fn, got "
+                              f"{getattr(t, 'dtype', type(t).__name__)}")
+        _req(t, torch.float8_e4m3fn, f"{name}.{which}")
+    inter = w_down8.shape[2] if w_down8.dim() == 3 else -1
+    if tuple(w_gu8.shape) != (E, 2 * inter, H) or tuple(w_down8.shape) != (E, H, inter):
+        raise HipOpsError(f"{name}: w_gu8 {tuple(w_gu8.shape)} / w_down8 {tuple(w_down8.shape)} are not "
+                          f"[E, 2I, H] / [E, H, I] for E {E}, H {H}")
+    if not isinstance(top_k, int) or not moe_supported(H, inter, E, top_k):
+        raise HipOpsError(f"{name}: unsupported shape (hidden {H}, inter {inter}, experts {E}, top_k {top_k}); "
+                          f"see moe_supported")
+    if T * top_k > MOE_MAX_PAIRS:
+        raise HipOpsError(f"{name}: {T} rows x top_k {top_k} exceed {MOE_MAX_PAIRS} pairs per launch")
+    nbi, nbh = -(-inter // MOE_W8_BLOCK), -(-H // MOE_W8_BLOCK)
+    for t, which, want in ((s_gu, "s_gu", (E, 2 * nbi, nbh)), (s_down, "s_down", (E, nbh, nbi))):
+        if not isinstance(t, torch.Tensor):
+            raise HipOpsError(f"{name}.{which}: expected a tensor")
+        _req(t, torch.float32, f"{name}.{which}")
+        if tuple(t.shape) != want or t.device != h.device:
+            raise HipOpsError(f"{name}.{which}: shape {tuple(t.shape)} on {t.device}, the weights need {want} "
+                              f"on {h.device}")
+    for t, which in ((w_router, "w_router"), (w_gu8, "w_gu8"), (w_down8, "w_down8")):
+        if t.device != h.device:
+            raise HipOpsError(f"{name}.{which}: on {t.device}, h is on {h.device}")
+        if t.data_ptr() % 16:
+            raise HipOpsError(f"{name}.{which}: must be 16-byte aligned")
+    return _moe_run(name, h, w_router, (w_gu8, s_gu, w_down8, s_down), T, H, inter, E, top_k, norm_topk, residual,
+                    norm_w, eps, workspace, out)

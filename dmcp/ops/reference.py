@@ -1083,3 +1083,98 @@ def moe_mlp(h: torch.Tensor, w_router: torch.Tensor, w_gu: torch.Tensor, w_down:
         out.copy_(m)
         return out
     return m
+
+
+# ---- block-scaled FP8 weights (the hub's ``quant_method: "fp8"`` layout with
+# ``weight_block_size: [128, 128]``).  A linear weight W [N, K] is stored as
+# ``X.weight`` in e4m3fn (torch.float8_e4m3fn) plus ``X.weight_scale_inv``, fp32
+# [ceil(N / 128), ceil(K / 128)]; despite the name the stored number is the
+# multiplier: W[n, k] = float(w8[n, k]) * scale_inv[n // 128, k // 128].  Edge
+# blocks are partial.  Leading axes (a stack of experts) pass through.
+#
+# The routed expert MLP's stacked tensors: w_gu8 [E, 2I, H] (gate rows, then up
+# rows) with s_gu [E, 2 ceil(I / 128), ceil(H / 128)] -- the gate's block rows
+# first, then the up's, each projection's blocks counted from its own row 0 --
+# and w_down8 [E, H, I] with s_down [E, ceil(H / 128), ceil(I / 128)].
+FP8_BLOCK = 128
+FP8_E4M3_MAX = 448.0
+
+
+def _block_expand(scale: torch.Tensor, rows: int, cols: int, block: int) -> torch.Tensor:
+    """One scale per element: [..., ceil(rows / b), ceil(cols / b)] -> [..., rows, cols]."""
+    return scale.repeat_interleave(block, dim=-2)[..., :rows, :].repeat_interleave(block, dim=-1)[..., :cols]
+
+
+def block_fp8_dequant(w8: torch.Tensor, scale_inv: torch.Tensor, dtype: torch.dtype = torch.float32,
+                      block: int = FP8_BLOCK) -> torch.Tensor:
+    """W = float(w8) * scale_inv[n // block, k // block], computed in fp32
+    (exact: an e4m3 value times an fp32 scale rounds once) and cast to ``dtype``."""
+    if w8.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"block_fp8_dequant: expected float8_e4m3fn, got {w8.dtype}")
+    rows, cols = w8.shape[-2:]
+    want = tuple(w8.shape[:-2]) + (-(-rows // block), -(-cols // block))
+    if tuple(scale_inv.shape) != want:
+        raise ValueError(f"block_fp8_dequant: scale_inv {tuple(scale_inv.shape)} does not match weight "
+                         f"{tuple(w8.shape)} (expected {want})")
+    return (w8.float() * _block_expand(scale_inv.float(), rows, cols, block)).to(dtype)
+
+
+def block_fp8_quant(w: torch.Tensor, block: int = FP8_BLOCK) -> tuple:
+    """(w8 e4m3fn, scale_inv fp32) of ``w`` [..., N, K]: per block scale =
+    amax / 448 (1 for an all-zero block), values divided by it, clamped to
+    +-448 and cast (round to nearest even)."""
+    rows, cols = w.shape[-2:]
+    nb, kb = -(-rows // block), -(-cols // block)
+    wf = w.float()
+    pad = torch.zeros(tuple(w.shape[:-2]) + (nb * block, kb * block), dtype=torch.float32, device=w.device)
+    pad[..., :rows, :cols] = wf.abs()
+    amax = pad.view(*w.shape[:-2], nb, block, kb, block).amax(dim=(-3, -1))
+    scale = torch.where(amax > 0, amax / FP8_E4M3_MAX, torch.ones_like(amax))
+    q = (wf / _block_expand(scale, rows, cols, block)).clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX)
+    return q.to(torch.float8_e4m3fn), scale
+
+
+def _moe_w8_check(h, w_router, w_gu8, s_gu, w_down8, s_down, top_k, name):
+    _moe_check(h, w_router, w_gu8, w_down8, top_k, name)
+    E, H = w_router.shape
+    inter = w_down8.shape[2]
+    for t, which in ((w_gu8, "w_gu8"), (w_down8, "w_down8")):
+        if t.dtype != torch.float8_e4m3fn:
+            raise ValueError(f"{name}: {which} must be float8_e4m3fn, got {t.dtype}")
+    nbi, nbh = -(-inter // FP8_BLOCK), -(-H // FP8_BLOCK)
+    for t, which, want in ((s_gu, "s_gu", (E, 2 * nbi, nbh)), (s_down, "s_down", (E, nbh, nbi))):
+        if t.dtype != torch.float32 or tuple(t.shape) != want:
+            raise ValueError(f"{name}: {which} is {t.dtype} {tuple(t.shape)}, expected float32 {want}")
+
+
+def moe_w8_dequant(w_gu8: torch.Tensor, s_gu: torch.Tensor, w_down8: torch.Tensor, s_down: torch.Tensor,
+                   dtype: torch.dtype = torch.float32) -> tuple:
+    """(w_gu [E, 2I, H], w_down [E, H, I]) of the stacked expert tensors: the
+    gate and up halves are dequantised each with its own block rows."""
+    inter = w_down8.shape[2]
+    nbi = s_gu.shape[1] // 2
+    gate = block_fp8_dequant(w_gu8[:, :inter], s_gu[:, :nbi], dtype)
+    up = block_fp8_dequant(w_gu8[:, inter:], s_gu[:, nbi:], dtype)
+    return torch.cat([gate, up], 1), block_fp8_dequant(w_down8, s_down, dtype)
+
+
+def moe_mlp_w8(h: torch.Tensor, w_router: torch.Tensor, w_gu8: torch.Tensor, s_gu: torch.Tensor,
+               w_down8: torch.Tensor, s_down: torch.Tensor, top_k: int, norm_topk: bool,
+               residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0,
+               workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`moe_mlp` over block-scaled FP8 expert weights, dequantised
+    exactly in fp32 (never rounded to bf16); activations stay bf16, with the
+    same bf16 rounding of act and of m and the same ``add_rmsnorm`` contract."""
+    _moe_w8_check(h, w_router, w_gu8, s_gu, w_down8, s_down, top_k, "moe_mlp_w8")
+    w_gu, w_down = moe_w8_dequant(w_gu8, s_gu, w_down8, s_down)
+    m = moe_mlp_math(h.float(), w_router.float(), w_gu, w_down, int(top_k), bool(norm_topk),
+                     round_act=lambda a: a.to(torch.bfloat16).float()).to(h.dtype)
+    if norm_w is not None:
+        return add_rmsnorm(m, norm_w, eps, residual=residual, out=out)
+    if residual is not None:
+        residual.copy_((m.float() + residual.float()).to(residual.dtype))
+        return residual
+    if out is not None:
+        out.copy_(m)
+        return out
+    return m

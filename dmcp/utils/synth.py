@@ -563,7 +563,7 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
 
 def qwen3_moe_checkpoint(root: str, n_experts: int = 8, experts_per_tok: int = 2, moe_intermediate: int = 128,
                          norm_topk: bool = True, experts_key: str = "num_experts", seed: int = 11,
-                         device: str = "cuda", **kw) -> str:
+                         device: str = "cuda", fp8: bool = False, **kw) -> str:
     """A Qwen3-MoE checkpoint directory in the hub layout: what
     :func:`llama_checkpoint` writes for ``model_type="qwen3"`` (``kw`` goes
     there: geometry, tokenizer, tied embeddings, ...) with every layer's dense
@@ -573,7 +573,14 @@ def qwen3_moe_checkpoint(root: str, n_experts: int = 8, experts_per_tok: int = 2
     probabilities differ visibly (a flat router would hide a loader that
     ignored ``norm_topk_prob`` or shuffled the experts).  ``experts_key``:
     ``num_experts`` (hub configs) or ``num_local_experts`` (what newer
-    ``transformers`` writes)."""
+    ``transformers`` writes).
+
+    ``fp8``: the hub's block-scaled FP8 layout of the same draws -- every
+    expert and q/k/v/o projection stored as ``F8_E4M3`` with an fp32
+    ``weight_scale_inv`` per 128 x 128 block
+    (:func:`dmcp.ops.reference.block_fp8_quant`), and ``quantization_config``
+    in ``config.json``; the router, norms, embeddings and ``lm_head`` stay
+    bf16.  Off, the files are byte for byte what they were."""
     import json
 
     import torch
@@ -598,6 +605,12 @@ def qwen3_moe_checkpoint(root: str, n_experts: int = 8, experts_per_tok: int = 2
             t[f"{p}experts.{e}.gate_proj.weight"] = rnd((moe_intermediate, hidden), 0.02)
             t[f"{p}experts.{e}.up_proj.weight"] = rnd((moe_intermediate, hidden), 0.02)
             t[f"{p}experts.{e}.down_proj.weight"] = rnd((hidden, moe_intermediate), out_std)
+    if fp8:
+        from ..ops.reference import block_fp8_quant
+        for n in [n for n in t if n.endswith("_proj.weight")]:
+            t[n], t[n + "_scale_inv"] = block_fp8_quant(t[n])
+        cfg["quantization_config"] = {"quant_method": "fp8", "fmt": "e4m3", "activation_scheme": "dynamic",
+                                      "weight_block_size": [128, 128]}
     save_file(t, f)
     cfg.update({"model_type": "qwen3_moe", "architectures": ["Qwen3MoeForCausalLM"], experts_key: n_experts,
                 "num_experts_per_tok": experts_per_tok, "moe_intermediate_size": moe_intermediate,

@@ -5,6 +5,14 @@ token) against the bf16 torch per-expert loop (index_select + F.linear +
 weighted index_add_) in the same process.
 
     python scripts/bench_moe.py [--rows 16,64,320,768,4096] [--iters 20] [--out profiles/moe_r7.jsonl]
+                                [--weights {bf16,fp8}] [--dequantised]
+
+``--weights fp8`` runs ops.moe_mlp_w8 over the same draws quantised to the
+block-scaled FP8 layout (ops.block_fp8_quant: e4m3 + one fp32 scale per
+128 x 128 block; 0.61 GB of experts); the torch loop then runs on the weights
+dequantised and rounded to bf16.  ``--weights bf16 --dequantised`` runs the
+bf16 kernel on those dequantised weights: the pair to alternate when the two
+formats are compared.
 
 Per row count: warm-up, then the median of ``--iters`` timings between events
 on one stream; one JSON line each with both times and the bytes/s the kernel
@@ -69,6 +77,9 @@ def main():
     ap.add_argument("--rows", default="16,64,320,768,4096")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default="")
+    ap.add_argument("--weights", choices=("bf16", "fp8"), default="bf16")
+    ap.add_argument("--dequantised", action="store_true",
+                    help="bf16 weights = the block-scaled FP8 quantisation of the draws, dequantised")
     a = ap.parse_args()
     from dmcp import ops
     g = torch.Generator(device="cuda").manual_seed(0)
@@ -79,6 +90,27 @@ def main():
     rows = [int(r) for r in a.rows.split(",")]
     ws = ops.moe_workspace(max(rows), H, I, E, K, "cuda")
     weight_bytes = E * 3 * I * H * 2
+    expert_bytes = 3 * I * H * 2
+    w8 = None
+    if a.weights == "fp8" or a.dequantised:
+        g8, gs = ops.block_fp8_quant(wgu[:, :I])
+        u8, us = ops.block_fp8_quant(wgu[:, I:])
+        d8, ds = ops.block_fp8_quant(wd)
+        w8 = (torch.cat([g8, u8], 1), torch.cat([gs, us], 1), d8, ds)
+        wgu, wd = ops.reference.moe_w8_dequant(*w8, dtype=torch.bfloat16)
+        del g8, u8, d8
+    if a.weights == "fp8":
+        scale_bytes = 4 * (w8[1][0].numel() + w8[3][0].numel())
+        expert_bytes = 3 * I * H + scale_bytes
+        weight_bytes = E * expert_bytes
+
+        def run(h, out):
+            return ops.moe_mlp_w8(h, wr, *w8, K, True, workspace=ws, out=out)
+    else:
+        w8 = None
+
+        def run(h, out):
+            return ops.moe_mlp(h, wr, wgu, wd, K, True, workspace=ws, out=out)
     lines = []
     for T in rows:
         h = rnd(T, H, std=1.0)
@@ -86,12 +118,13 @@ def main():
         # compared under the kernel's own routing: the figure is then the two
         # GEMM pipelines' bf16 rounding, not rows that chose other experts
         ref, ids = torch_loop(h, wr, wgu, wd, ops.moe_route(h, wr, K, True))
-        got = ops.moe_mlp(h, wr, wgu, wd, K, True, workspace=ws, out=out)
+        got = run(h, out)
         err = ((got.float() - ref.float()).abs().max() / ref.float().abs().max()).item()
-        touched = ids.unique().numel() * 3 * I * H * 2
-        k_med, k_min = timed(lambda: ops.moe_mlp(h, wr, wgu, wd, K, True, workspace=ws, out=out), a.iters)
+        touched = ids.unique().numel() * expert_bytes
+        k_med, k_min = timed(lambda: run(h, out), a.iters)
         l_med, l_min = timed(lambda: torch_loop(h, wr, wgu, wd), max(3, a.iters // 4), warmup=2)
-        rec = {"bench": "moe_mlp", "rows": T, "hidden": H, "inter": I, "experts": E, "top_k": K,
+        rec = {"bench": "moe_mlp" if a.weights == "bf16" else "moe_mlp_w8", "weights": a.weights,
+               "dequantised": bool(a.dequantised or a.weights == "fp8"), "rows": T, "hidden": H, "inter": I, "experts": E, "top_k": K,
                "kernel_us": round(k_med, 1), "kernel_min_us": round(k_min, 1), "torch_loop_us": round(l_med, 1),
                "torch_loop_min_us": round(l_min, 1), "speedup": round(l_med / k_med, 2),
                "weights_gb": round(weight_bytes / 1e9, 3), "touched_gb": round(touched / 1e9, 3),
