@@ -324,9 +324,10 @@ class GpuWorkerPool:
                     who.info = msg
                     self._rebalance()
                 wit = msg.get("witness") or {}
-                LOG.info("GPU worker %d ready on %s (pid %s, chat template %s, KV cache %s%s)", who.index, who.device,
-                         msg.get("pid"), wit.get("chat_template", "n/a"), wit.get("kv_dtype", "n/a"),
-                         f", moe={wit['moe']} moe_weights={wit.get('moe_weights', 'bf16')}" if wit.get("moe") else "")
+                LOG.info("GPU worker %d ready on %s (pid %s, chat template %s, KV cache %s%s%s)", who.index,
+                         who.device, msg.get("pid"), wit.get("chat_template", "n/a"), wit.get("kv_dtype", "n/a"),
+                         f", moe={wit['moe']} moe_weights={wit.get('moe_weights', 'bf16')}" if wit.get("moe") else "",
+                         f", window={wit['window']}" if wit.get("window") else "")
         if not any(w.ready and w.alive for w in self.workers):
             raise RuntimeError("no GPU worker started")
         self._initialised = True
@@ -737,6 +738,9 @@ def _witness(dev: str, model=None) -> dict:
         kv["moe"] = f"{model.cfg.n_experts}x{model.cfg.experts_per_tok}"
         # the experts' weight format: block-scaled e4m3 (128 x 128 blocks) or bf16
         kv["moe_weights"] = "fp8b128" if getattr(model.cfg, "moe_weight_dtype", "bf16") == "fp8b" else "bf16"
+    if model is not None and getattr(model, "windows", None):  # sliding-window layers: "4096@all", "4096@28.."
+        from ..models.llm import windows_label
+        kv["window"] = windows_label(model.windows)
     if not dev.startswith("cuda"):
         return {"device": dev, **kv}
     try:
@@ -793,7 +797,8 @@ def worker_main() -> int:
         max_batch = model.cfg.max_batch
     witness = _witness(dev, model)
     if model is not None:
-        LOG.info("worker %d on %s: KV cache %s", os.getpid(), dev, model.cfg.kv_dtype)
+        LOG.info("worker %d on %s: KV cache %s%s", os.getpid(), dev, model.cfg.kv_dtype,
+                 f", sliding window {witness['window']}" if "window" in witness else "")
     if hasattr(eng, "chat_mode"):  # "raw" or "template:<file>": what the prompts are wrapped in
         witness["chat_template"] = eng.chat_mode
         LOG.info("worker %d on %s: chat template %s", os.getpid(), dev, eng.chat_mode)

@@ -120,6 +120,12 @@ class LMConfig:
     # as a block-scaled FP8 checkpoint stores them.  Set by the loader from the
     # checkpoint; a random-init preset with "fp8b" quantises its random experts
     moe_weight_dtype: str = "bf16"
+    # sliding-window attention (Mistral; Qwen2 / Qwen3 with use_sliding_window):
+    # one int per layer, the keys a query attends including its own (0 = every
+    # key); None = full attention in every layer.  The loader resolves it from
+    # sliding_window / max_window_layers / layer_types (checkpoint_windows); a
+    # window >= max_seq is stored as 0.  The KV cache stays linear.
+    layer_windows: Optional[tuple] = None
 
     @property
     def qkv_dim(self) -> int:
@@ -216,11 +222,94 @@ class CheckpointUnsupported(ValueError):
     (:func:`check_checkpoint` gives the reason)."""
 
 
-SUPPORTED_MODEL_TYPES = ("llama", "qwen2", "qwen3", "qwen3_moe")
-SUPPORTED_ARCHITECTURES = ("LlamaForCausalLM", "Qwen2ForCausalLM", "Qwen3ForCausalLM", "Qwen3MoeForCausalLM")
+SUPPORTED_MODEL_TYPES = ("llama", "qwen2", "qwen3", "qwen3_moe", "mistral")
+SUPPORTED_ARCHITECTURES = ("LlamaForCausalLM", "Qwen2ForCausalLM", "Qwen3ForCausalLM", "Qwen3MoeForCausalLM",
+                           "MistralForCausalLM")
 MOE_ARCHITECTURE = "Qwen3MoeForCausalLM"
+MISTRAL_ARCHITECTURE = "MistralForCausalLM"
+_LAYER_TYPES = ("full_attention", "sliding_attention")
 _DENSE_MLP = ("mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
 _EXPERT_PROJS = ("gate_proj", "up_proj", "down_proj")
+
+
+def _positive_int(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool) and v > 0
+
+
+def checkpoint_windows(hf: dict) -> Tuple[Optional[tuple], Optional[str]]:
+    """(one sliding window per layer -- 0 = full attention -- or None when no
+    layer has one, None) of a config.json, or (None, reason) naming the key.
+
+    * ``layer_types``, when present, decides per layer: ``sliding_attention``
+      takes ``sliding_window``, ``full_attention`` none;
+    * else ``model_type`` "mistral": a positive-integer ``sliding_window``
+      applies to every layer (null / absent: none);
+    * else (qwen2 / qwen3 / qwen3_moe) ``use_sliding_window`` true: the layers
+      ``i >= max_window_layers`` take ``sliding_window``."""
+    n = hf["num_hidden_layers"]
+    sw = hf.get("sliding_window")
+    lt = hf.get("layer_types")
+    mt = hf.get("model_type")
+    if hf.get("use_sliding_window"):  # whatever decides the layers, the switch needs a window to switch on
+        if mt not in ("qwen2", "qwen3", "qwen3_moe"):
+            return None, (f"use_sliding_window true is not supported for model_type {mt!r} "
+                          f"(qwen2 / qwen3 / qwen3_moe read it)")
+        if not _positive_int(sw):
+            return None, (f"use_sliding_window is true but sliding_window is {sw!r} (a positive integer is "
+                          f"needed)")
+    if lt:
+        other = sorted({str(t) for t in lt if t not in _LAYER_TYPES})
+        if other:
+            return None, (f"layer_types contains {', '.join(other)} (supported: {', '.join(_LAYER_TYPES)})")
+        if len(lt) != n:
+            return None, f"layer_types has {len(lt)} entries, num_hidden_layers is {n}"
+        if "sliding_attention" not in lt:
+            return None, None
+        if not _positive_int(sw):
+            return None, (f"layer_types contains sliding_attention but sliding_window is {sw!r} "
+                          f"(a positive integer is needed)")
+        return tuple(sw if t == "sliding_attention" else 0 for t in lt), None
+    if mt == "mistral":
+        if sw is None:
+            return None, None
+        if not _positive_int(sw):
+            return None, f"sliding_window is {sw!r} (a positive integer or null is needed)"
+        return (sw,) * n, None
+    if hf.get("use_sliding_window"):
+        mwl = hf.get("max_window_layers", n)
+        if not isinstance(mwl, int) or isinstance(mwl, bool) or mwl < 0:
+            return None, f"use_sliding_window is true but max_window_layers is {mwl!r} (an integer >= 0 is needed)"
+        wins = tuple(sw if i >= mwl else 0 for i in range(n))
+        return (wins if any(wins) else None), None
+    return None, None
+
+
+def resolve_windows(windows: Optional[tuple], max_seq: int) -> Optional[tuple]:
+    """``windows`` as the model runs them in slots of ``max_seq`` positions: a
+    window that no sequence can outgrow is 0 (today's kernels, untouched);
+    None when no layer is left with one."""
+    if not windows:
+        return None
+    out = tuple(0 if w >= max_seq else int(w) for w in windows)
+    return out if any(out) else None
+
+
+def windows_label(windows: Optional[tuple]) -> str:
+    """The resolved windows for logs and the worker witness: "none",
+    "4096@all", "4096@28.." (from layer 28 on) or "4096@0,2,4"."""
+    if not windows or not any(windows):
+        return "none"
+    parts = []
+    for w in sorted({w for w in windows if w}):
+        idx = [i for i, x in enumerate(windows) if x == w]
+        if len(idx) == len(windows):
+            where = "all"
+        elif idx == list(range(idx[0], len(windows))):
+            where = f"{idx[0]}.."
+        else:
+            where = ",".join(str(i) for i in idx)
+        parts.append(f"{w}@{where}")
+    return "+".join(parts)
 
 
 def _moe_config(hf: dict) -> Tuple[Optional[tuple], Optional[str]]:
@@ -429,12 +518,13 @@ def check_checkpoint(path: str, chat_template: Optional[str] = "auto") -> Option
         return f"hidden_act {act!r} is not supported (the MLP kernels compute SwiGLU with silu)"
     if hf.get("mlp_bias"):
         return "mlp_bias true is not supported (the MLP projections take no bias)"
-    if hf.get("use_sliding_window"):
-        return "use_sliding_window true is not supported (the attention kernels attend to every cached key)"
-    other = sorted({str(t) for t in hf.get("layer_types") or [] if t != "full_attention"})
-    if other:
-        return (f"layer_types contains {', '.join(other)} (only full_attention is supported: the attention "
-                f"kernels attend to every cached key)")
+    if archs and (MISTRAL_ARCHITECTURE in archs) != (mt == "mistral") or (mt == "mistral" and len(archs) > 1):
+        if mt == "mistral":
+            return f"model_type 'mistral' does not match architectures {archs!r} (expected [{MISTRAL_ARCHITECTURE!r}])"
+        return f"architectures {archs!r} does not match model_type {mt!r}"
+    _, why = checkpoint_windows(hf)
+    if why is not None:
+        return why
     heads = hf["num_attention_heads"]
     kvh = hf.get("num_key_value_heads", heads)
     if not isinstance(kvh, int) or kvh <= 0 or heads % kvh:
@@ -685,6 +775,15 @@ class LocalLM:
             if ("l0.we_gu8" in self.w) != self.moe_w8:
                 raise ValueError(f"{cfg.name}: moe_weight_dtype {cfg.moe_weight_dtype!r} does not match the weights "
                                  f"({'l0.we_gu8' if 'l0.we_gu8' in self.w else 'l0.we_gu'})")
+        # sliding windows: _wkw(i) is layer i's extra attention keyword -- empty
+        # for a full-attention layer, so such layers (and whole models) make
+        # the calls they always made and never reach a windowed entry point
+        lw = cfg.layer_windows
+        if lw is not None:
+            if len(lw) != cfg.layers or any(isinstance(w, bool) or not isinstance(w, int) or w < 0 for w in lw):
+                raise ValueError(f"{cfg.name}: layer_windows must hold one integer >= 0 per layer "
+                                 f"({cfg.layers}), got {lw!r}")
+        self.windows = tuple(lw) if lw is not None and any(lw) else None
         self._fold_norms()
         c = cfg
         # the routed MLP's scratch, once, like attn_ws / wgemm_ws: decode steps
@@ -965,6 +1064,8 @@ class LocalLM:
         if moe is not None:
             cfg = replace(cfg, n_experts=moe[0], experts_per_tok=moe[1], moe_intermediate=moe[2], norm_topk=moe[3])
         cfg = replace(cfg, **cfg_overrides)
+        if "layer_windows" not in cfg_overrides:  # against the slots' capacity, overrides applied
+            cfg = replace(cfg, layer_windows=resolve_windows(checkpoint_windows(hf)[0], cfg.max_seq))
         fp8 = _fp8_config(hf)[0]
         if cfg.prefill_dtype == "auto" and not MXFP8_CHECKPOINT_OK:
             # a real checkpoint keeps bf16 prefill GEMMs unless fp8 is asked
@@ -1051,6 +1152,11 @@ class LocalLM:
             return None
         return self.w[f"l{i}.qnorm"], self.w[f"l{i}.knorm"], self.cfg.eps
 
+    def _wkw(self, i: int) -> dict:
+        """Layer i's ``window`` keyword of the attention ops: empty for full attention."""
+        w = self.windows[i] if self.windows else 0
+        return {"window": w} if w else {}
+
     def _kvs(self, i: int) -> Optional[tuple]:
         """Layer i's ``kv_scale`` argument of the KV ops: its rows of the
         exponent tables, None for the unscaled formats."""
@@ -1122,9 +1228,12 @@ class LocalLM:
             kvs = self._kvs(i)
             q = ops.rope_kv(qkv, pos, slots, self.cos_sin, kc, vc, c.n_heads, qk_norm=self._qk_norm(i),
                             kv_scale=kvs)  # [T, Hq, D]
-            if self.use_prefill_kernel:
-                att = ops.prefill_attention(q, kc, vc, slot, start_pos, self.prefix_slot if shared else None,
-                                            shared, self.scale, kv_scale=kvs)
+            if self.use_prefill_kernel or self._wkw(i):
+                # (a windowed layer off the kernel's shapes or on the CPU: the
+                # fp32 reference of the same op -- SDPA below has no window)
+                pf = ops.prefill_attention if self.use_prefill_kernel else ops.reference.prefill_attention
+                att = pf(q, kc, vc, slot, start_pos, self.prefix_slot if shared else None,
+                         shared, self.scale, kv_scale=kvs, **self._wkw(i))
                 o = F.linear(att.view(T, c.n_heads * c.head_dim), self.w[f"l{i}.wo"])
             else:
                 k = _kv_bf16(kc[slot, :, :L], kvs[0][slot, :, :L] if kvs else None).unsqueeze(0)  # [1, Hkv, L, D]
@@ -1209,7 +1318,7 @@ class LocalLM:
             q = ops.rope_kv(qkv, pos_t, slot_t, self.cos_sin, kc, vc, c.n_heads,
                             qk_norm=self._qk_norm(i), kv_scale=kvs)  # [Ttot, Hq, D]
             att = ops.prefill_attention_varlen(q, kc, vc, offsets, seq_slots, starts, prefix, shared, self.scale,
-                                               kv_scale=kvs)
+                                               kv_scale=kvs, **self._wkw(i))
             o = F.linear(att.view(Ttot, c.n_heads * c.head_dim), self.w[f"l{i}.wo"])
             h = ops.add_rmsnorm(o, self.w[f"l{i}.ln2"], c.eps, residual=resid)
             nxt = self.w[f"l{i + 1}.ln1"] if i + 1 < c.layers else self.w["norm_f"]
@@ -1239,7 +1348,8 @@ class LocalLM:
         for i in range(c.layers):
             kc, vc = self.k_cache[i], self.v_cache[i]
             q = ops.pgemm_qkv(aq, as_, *self.w8[f"l{i}.wqkv"], pos_t, slot_t, self.cos_sin, kc, vc, c.n_heads)
-            att = ops.prefill_attention_varlen(q, kc, vc, offsets, seq_slots, starts, prefix, shared, self.scale)
+            att = ops.prefill_attention_varlen(q, kc, vc, offsets, seq_slots, starts, prefix, shared, self.scale,
+                                               **self._wkw(i))
             ops.mx_quant(att.view(T, c.hidden), aq, as_)
             ops.pgemm_resid(aq, as_, *self.w8[f"l{i}.wo"], resid)
             ops.rmsnorm_mx(resid, self._g(f"l{i}.ln2"), c.eps, q=aq, s=as_)
@@ -1309,7 +1419,7 @@ class LocalLM:
                                 c.n_heads, qk_norm=qkn, kv_scale=kvs)
             att = ops.decode_attention(q, kc, vc, slots, seq_len, self.scale, workspace=self.attn_ws, chunk=chunk,
                                        fork=self.fork_tab, prefix=self._prefix(i, prefix_rows), splits=splits,
-                                       kv_scale=kvs).view(B, c.n_heads * c.head_dim)
+                                       kv_scale=kvs, **self._wkw(i)).view(B, c.n_heads * c.head_dim)
             if big:
                 h = ops.tgemm_resid_norm(att, self.w[f"l{i}.wo"], resid, self.w[f"l{i}.ln2"], c.eps, self.tg_ws)
             elif wide:
@@ -1352,7 +1462,8 @@ class LocalLM:
                 q = ops.pgemm_qkv(xq, xs, *w8[f"l{i}.wqkv"], positions, slots, self.cos_sin, kc, vc, c.n_heads)
             att = ops.decode_attention(q, kc, vc, slots, seq_len, self.scale, workspace=self.attn_ws, chunk=chunk,
                                        fork=self.fork_tab,
-                                       prefix=self._prefix(i, prefix_rows), splits=splits).view(B, c.hidden)
+                                       prefix=self._prefix(i, prefix_rows), splits=splits,
+                                       **self._wkw(i)).view(B, c.hidden)
             aq, as_ = ops.mx_quant(att)
             if gpu:
                 xq, xs = ops.wgemm_mx_resid_norm(aq, as_, *w8[f"l{i}.wo"], resid, self._g(f"l{i}.ln2"), c.eps,
@@ -1412,7 +1523,8 @@ class LocalLM:
                                       c.n_heads, bias=self.w.get(f"l{i}.bqkv"))
             att = ops.decode_attention(q, kc, vc, slots, seq_len, self.scale, workspace=self.attn_ws, chunk=chunk,
                                        fork=self.fork_tab,
-                                       prefix=self._prefix(i, prefix_rows), splits=splits, kv_scale=kvs)
+                                       prefix=self._prefix(i, prefix_rows), splits=splits, kv_scale=kvs,
+                                       **self._wkw(i))
             ops.fused_resid(att.view(B, c.n_heads * c.head_dim), self.w[f"l{i}.wo"], r)
             if self.moe:
                 # the norm fused_swiglu folds into its prologue, explicit: the
@@ -1713,6 +1825,9 @@ class LocalLM:
             v = v.repeat_interleave(G, dim=1)
             att = torch.einsum("thd,shd->hts", q, k) * self.scale
             att = att.masked_fill(torch.triu(torch.ones(T, T, dtype=torch.bool, device=dev), 1), float("-inf"))
+            if self._wkw(i):  # key j of query t only while j > t - window
+                att = att.masked_fill(torch.tril(torch.ones(T, T, dtype=torch.bool, device=dev),
+                                                 -self.windows[i]), float("-inf"))
             o = torch.einsum("hts,shd->thd", torch.softmax(att, -1), v).reshape(T, -1)
             x = x + o @ w[f"l{i}.wo"].t()
             h = rms(x, w[f"l{i}.ln2"])

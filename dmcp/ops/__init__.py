@@ -70,13 +70,17 @@ del _name
 
 
 def decode_attention(q, k_cache, v_cache, slot, seq_len, scale, workspace=None, chunk: int = 256, out=None,
-                     prefix=None, splits=None, fork=None, kv_scale=None):
-    """Per-row decode attention; the CPU reference takes no split count."""
+                     prefix=None, splits=None, fork=None, kv_scale=None, window: int = 0):
+    """Per-row decode attention; the CPU reference takes no split count.
+    ``window`` > 0: sliding-window attention (0 = every key, the call as it was)."""
     if q.is_cuda:
+        if not window:
+            return hip.decode_attention(q, k_cache, v_cache, slot, seq_len, scale, workspace, chunk, out, prefix,
+                                        splits, fork, kv_scale)
         return hip.decode_attention(q, k_cache, v_cache, slot, seq_len, scale, workspace, chunk, out, prefix, splits,
-                                    fork, kv_scale)
+                                    fork, kv_scale, window)
     return reference.decode_attention(q, k_cache, v_cache, slot, seq_len, scale, workspace, chunk, out, prefix, fork,
-                                      kv_scale)
+                                      kv_scale, window)
 
 
 # GPU-only fused GEMM with a shape-dependent default

@@ -26,6 +26,14 @@ hipError_t dmcp_launch_prefix_partials_scaled(const uint16_t* q, const void* pk,
                                               int nsplit, int splits_total, float sl2, const uint8_t* pks,
                                               const uint8_t* pvs, hipStream_t st);
 
+// the same under a sliding window (prefill_attn.hip): row b sees the prefix keys
+// [max(0, min(seq_len[b], ldk) - window), *plen) only; pks / pvs nullptr = an
+// unscaled prefix (kv8 tells bf16 from fp8)
+hipError_t dmcp_launch_prefix_partials_window(const uint16_t* q, const void* pk, const void* pv, const int32_t* plen,
+                                              float* part_o, float* part_ml, int B, int Hkv, int G, int D, int ldk,
+                                              int nsplit, int splits_total, float sl2, int kv8, const uint8_t* pks,
+                                              const uint8_t* pvs, const int32_t* seq_len, int window, hipStream_t st);
+
 namespace {
 
 // Per-row split geometry, shared by the per-row kernels and the combine:
@@ -227,7 +235,10 @@ __global__ __launch_bounds__(kBlock) void rope_kv_kernel(const uint16_t* __restr
 // pass runs only for steps of more than one split per row.  (A fused "last block merges" variant needs agent-scope release
 // fences; on gfx950 each one writes back the XCD's L2 and made the kernel
 // ~10x slower -- profiles/ROUND1_NOTES.md.)
-template <int D>
+// WIN (sliding window): the row's own splits were cut from [max(P, L - window), L)
+// -- the same span the main kernel used; the prefix partials of a row whose
+// window starts at or past P are empty (m = -1e30, l = 0) and weigh 0.
+template <int D, bool WIN = false>
 __global__ __launch_bounds__(kBlock) void decode_attn_combine_kernel(const float* __restrict__ part_o,
                                                                     const float* __restrict__ part_ml,
                                                                     const int32_t* __restrict__ slot,
@@ -235,7 +246,8 @@ __global__ __launch_bounds__(kBlock) void decode_attn_combine_kernel(const float
                                                                     uint16_t* __restrict__ out, int B, int Hq,
                                                                     int max_seq, int chunk, int splits,
                                                                     int num_slots, const int32_t* __restrict__ plen,
-                                                                    int ps_max, const int32_t* __restrict__ prow) {
+                                                                    int ps_max, const int32_t* __restrict__ prow,
+                                                                    int window = 0) {
     constexpr int U = 8;
     constexpr int DQ = D / 4;       // lanes per partial group
     constexpr int PG = kWave / DQ;  // partial groups per wave
@@ -255,7 +267,7 @@ __global__ __launch_bounds__(kBlock) void decode_attn_combine_kernel(const float
         // the shared prefix's ps_max partials (prefill kernel in prefix mode;
         // splits past the prefix's end are empty and weigh 0)
         const int npre = P > 0 ? ps_max : 0;
-        const int nact = split_geom(L - P, splits, chunk).nact;
+        const int nact = split_geom(L - (WIN ? max(P, L - window) : P), splits, chunk).nact;
         if (nact <= 1) continue;  // finished by the main kernel (directly, or merging the prefix partials)
         const int n = npre + nact;
         const size_t base = ((size_t)b * Hq + qh) * splits_total;
@@ -901,15 +913,21 @@ __device__ __forceinline__ void attn_tile_mfma(KVTile<D, KV8>& cur, KVScl<D, SC>
 //    instructions per tile but not time (the kernel waits on memory).
 //    No block-level synchronisation: each wave owns its LDS tile, so
 //    different waves of a block run different items.
+//    WIN (sliding window, a separate set of instantiations): a row of live
+//    length L attends keys [L - window, L) of its logical sequence, so this
+//    kernel covers [max(P, L - window), L) and the equal splits are cut from
+//    that span (never from L: a windowed row has no empty split); the first
+//    tile starts at the exact key, as it does behind a prefix.  Every key's
+//    source (own slot / fork parent) is resolved by its position as before.
 // --------------------------------------------------------------------------
-template <int D, bool KV8, bool SC = false>
+template <int D, bool KV8, bool SC = false, bool WIN = false>
 __global__ __launch_bounds__(kBlock) void decode_attn_mfma_kernel(
     const uint16_t* __restrict__ q, const void* __restrict__ k_cache, const void* __restrict__ v_cache,
     const int32_t* __restrict__ slot, const int32_t* __restrict__ seq_len, uint16_t* __restrict__ out,
     float* __restrict__ part_o, float* __restrict__ part_ml, int B, int Hkv, int G,
     int max_seq, int chunk, int splits, float scale_log2, int num_slots, const int32_t* __restrict__ plen,
     int ps_max, const int32_t* __restrict__ prow, const int32_t* __restrict__ fork,
-    const uint8_t* __restrict__ k_scale = nullptr, const uint8_t* __restrict__ v_scale = nullptr) {
+    const uint8_t* __restrict__ k_scale = nullptr, const uint8_t* __restrict__ v_scale = nullptr, int window = 0) {
     static_assert(D % 32 == 0, "D must be a multiple of 32");
     static_assert(KV8 || !SC, "scaled caches are fp8");
     constexpr int KS = D / 32;    // 32-dim k-steps of the S product
@@ -953,14 +971,16 @@ __global__ __launch_bounds__(kBlock) void decode_attn_mfma_kernel(
         }
         // a row outside the shared prefix (prow[b] == 0) owns all its keys
         const int P = __builtin_amdgcn_readfirstlane((prow && !prow[b]) ? 0 : P0);
-        const SplitGeom sg = split_geom(L - P, splits, chunk);
+        // the first key this kernel reads: the prefix's end, or the window's
+        const int base = WIN ? max(P, L - window) : P;
+        const SplitGeom sg = split_geom(L - base, splits, chunk);
         if (split >= max(1, sg.nact)) continue;
         // one own split: this wave writes the row's final output -- directly,
         // or (shared prefix) after merging the prefix kernel's partials, which
         // the same stream finished before this launch (no combine pass)
         const bool direct = P == 0 && sg.nact == 1;
         const bool merge_prefix = P > 0 && sg.nact <= 1;
-        const int start = P + split * sg.part;
+        const int start = base + split * sg.part;
         const int end = min(L, start + sg.part);
         const int ntiles = (end - start + 31) / 32;
         bf16x8_t qf[KS];
@@ -1074,11 +1094,19 @@ inline int grid_for(size_t work) {
 
 hipError_t launch_combine(void* part_o, void* part_ml, const int32_t* sl, const int32_t* ln, void* out, int B, int Hq,
                           int D, int max_seq, int chunk, int splits, int num_slots, const int32_t* pl, int ps_max,
-                          const int32_t* pr, hipStream_t st) {
+                          const int32_t* pr, hipStream_t st, int window = 0) {
     const int waves = B * Hq;
     const int blocks = (waves + 3) / 4;
     const dim3 grid((unsigned)(blocks < 2048 ? blocks : 2048));
-    if (D == 64)
+    if (window > 0 && D == 64)
+        decode_attn_combine_kernel<64, true><<<grid, kBlock, 0, st>>>(
+            (const float*)part_o, (const float*)part_ml, sl, ln, (uint16_t*)out, B, Hq, max_seq, chunk, splits,
+            num_slots, pl, ps_max, pr, window);
+    else if (window > 0 && D == 128)
+        decode_attn_combine_kernel<128, true><<<grid, kBlock, 0, st>>>(
+            (const float*)part_o, (const float*)part_ml, sl, ln, (uint16_t*)out, B, Hq, max_seq, chunk, splits,
+            num_slots, pl, ps_max, pr, window);
+    else if (D == 64)
         decode_attn_combine_kernel<64><<<grid, kBlock, 0, st>>>((const float*)part_o, (const float*)part_ml, sl, ln,
                                                                (uint16_t*)out, B, Hq, max_seq, chunk, splits,
                                                                num_slots, pl, ps_max, pr);
@@ -1240,8 +1268,10 @@ static int decode_attention_launch(const void* q, const void* k_cache, const voi
                                    int D, int max_seq, int num_slots, int chunk, int splits, float scale,
                                    const void* prefix_k, const void* prefix_v, const void* plen, int ps_max, int kv8,
                                    const void* prefix_rows, const void* fork, void* stream, const uint8_t* k_scale,
-                                   const uint8_t* v_scale, const uint8_t* prefix_ks, const uint8_t* prefix_vs) {
+                                   const uint8_t* v_scale, const uint8_t* prefix_ks, const uint8_t* prefix_vs,
+                                   int window = 0) {
     if (B <= 0) return 0;
+    if (window < 0) return hipErrorInvalidValue;
     if (Hkv <= 0 || Hq % Hkv != 0 || splits <= 0 || chunk <= 0 || !(D == 64 || D == 128) || Hq / Hkv > 16)
         return hipErrorInvalidValue;
     const bool prefix = plen != nullptr;
@@ -1258,7 +1288,10 @@ static int decode_attention_launch(const void* q, const void* k_cache, const voi
     auto pr = prefix ? (const int32_t*)prefix_rows : nullptr;
     if (prefix) {
         hipError_t pe =
-            k_scale ? dmcp_launch_prefix_partials_scaled(qq, prefix_k, prefix_v, pl, (float*)part_o, (float*)part_ml,
+            window  ? dmcp_launch_prefix_partials_window(qq, prefix_k, prefix_v, pl, (float*)part_o, (float*)part_ml,
+                                                         B, Hkv, G, D, max_seq, ps_max, ps_max + splits, sl2, kv8,
+                                                         prefix_ks, prefix_vs, ln, window, st)
+            : k_scale ? dmcp_launch_prefix_partials_scaled(qq, prefix_k, prefix_v, pl, (float*)part_o, (float*)part_ml,
                                                          B, Hkv, G, D, max_seq, ps_max, ps_max + splits, sl2,
                                                          prefix_ks, prefix_vs, st)
                     : dmcp_launch_prefix_partials(qq, prefix_k, prefix_v, pl, (float*)part_o, (float*)part_ml, B, Hkv,
@@ -1286,9 +1319,20 @@ static int decode_attention_launch(const void* q, const void* k_cache, const voi
         const dim3 wgrid((unsigned)(wblocks < cap ? wblocks : cap));                                               \
         decode_attn_mfma_kernel<DD, K8, ##__VA_ARGS__><<<wgrid, kBlock, 0, st>>>(                                  \
             qq, k_cache, v_cache, sl, ln, oo, po, pml, B, Hkv, G, max_seq, chunk, splits, sl2, num_slots, pl,      \
-            ps_max, pr, (const int32_t*)fork, k_scale, v_scale);                                                   \
+            ps_max, pr, (const int32_t*)fork, k_scale, v_scale, window);                                           \
     } while (0)
-    if (k_scale) {
+    if (window > 0) {  // the sliding-window instantiations
+        if (k_scale) {
+            if (D == 64) DMCP_MFMA_DECODE(64, true, true, true);
+            else DMCP_MFMA_DECODE(128, true, true, true);
+        } else if (kv8) {
+            if (D == 64) DMCP_MFMA_DECODE(64, true, false, true);
+            else DMCP_MFMA_DECODE(128, true, false, true);
+        } else {
+            if (D == 64) DMCP_MFMA_DECODE(64, false, false, true);
+            else DMCP_MFMA_DECODE(128, false, false, true);
+        }
+    } else if (k_scale) {
         if (D == 64) DMCP_MFMA_DECODE(64, true, true);
         else DMCP_MFMA_DECODE(128, true, true);
     } else if (kv8) {
@@ -1302,7 +1346,7 @@ static int decode_attention_launch(const void* q, const void* k_cache, const voi
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || splits == 1) return e;  // every row finished in the main kernel
     return launch_combine(part_o, part_ml, sl, ln, out, B, Hq, D, max_seq, chunk, splits, num_slots, pl, ps_max, pr,
-                          st);
+                          st, window);
 }
 
 int dmcp_decode_attention(const void* q, const void* k_cache, const void* v_cache, const void* slot,
@@ -1329,6 +1373,26 @@ int dmcp_decode_attention_scaled(const void* q, const void* k_cache, const void*
                                    num_slots, chunk, splits, scale, prefix_k, prefix_v, plen, ps_max, 1, prefix_rows,
                                    fork, stream, (const uint8_t*)k_scale, (const uint8_t*)v_scale,
                                    (const uint8_t*)prefix_ks, (const uint8_t*)prefix_vs);
+}
+
+// dmcp_decode_attention / _scaled under a sliding window (window >= 1): a row
+// of live length L attends keys [max(0, L - window), L) of its logical
+// sequence.  One entry point for the three cache formats: k_scale / v_scale
+// (and, with plen, prefix_ks / prefix_vs) both given = per-row scaled fp8,
+// nullptr = bf16 (kv8 0) or unit-scale fp8 (kv8 1).
+int dmcp_decode_attention_window(const void* q, const void* k_cache, const void* v_cache, const void* slot,
+                                 const void* seq_len, void* out, void* part_o, void* part_ml, int B, int Hq, int Hkv,
+                                 int D, int max_seq, int num_slots, int chunk, int splits, float scale,
+                                 const void* prefix_k, const void* prefix_v, const void* plen, int ps_max, int kv8,
+                                 const void* prefix_rows, const void* fork, void* stream, const void* k_scale,
+                                 const void* v_scale, const void* prefix_ks, const void* prefix_vs, int window) {
+    if (window < 1 || (!k_scale != !v_scale) || (k_scale && (!kv8 || (plen && (!prefix_ks || !prefix_vs)))))
+        return hipErrorInvalidValue;
+    return decode_attention_launch(q, k_cache, v_cache, slot, seq_len, out, part_o, part_ml, B, Hq, Hkv, D, max_seq,
+                                   num_slots, chunk, splits, scale, prefix_k, prefix_v, plen, ps_max, kv8, prefix_rows,
+                                   fork, stream, (const uint8_t*)k_scale, (const uint8_t*)v_scale,
+                                   k_scale ? (const uint8_t*)prefix_ks : nullptr,
+                                   k_scale ? (const uint8_t*)prefix_vs : nullptr, window);
 }
 
 int dmcp_silu_mul(const void* gu, void* out, int T, int I, void* stream) {

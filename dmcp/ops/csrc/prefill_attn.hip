@@ -85,16 +85,38 @@ struct PfScale<true> {
     const uint8_t* pv;
 };
 
+// Sliding window (WIN): a query at position i sees keys (i - window, i] of the
+// logical sequence.  In prefix mode the query of row b sits at position
+// min(seq_len[b], ldk) - 1 (its live length, read in the kernel), so its
+// visible prefix keys are [max(0, L_b - window), *plen).  Empty for full
+// attention -- those instantiations take no argument bytes and no code for it.
+template <bool WIN>
+struct PfWin {};
+
+template <>
+struct PfWin<true> {
+    int window;
+    const int32_t* seq_len;  // prefix mode only: int32 [T] live lengths
+};
+
 // The work of one block: kv head kh, column tile ct (32 * NSUB * NWAVE query
 // columns), key split sp of nsplit.  Shared by the single-sequence kernel,
 // the varlen (packed multi-sequence) kernel and the decode step's prefix mode.
-template <int D, int NSUB, int NWAVE, bool KV8, bool SC = false>
+//
+// WIN: each lane keeps the lowest key its column sees (qlo); per 32-column unit
+// the smallest and largest of them (wave reductions, once per block) decide,
+// as scalars, which 32-key tiles are skipped (wholly below every column's
+// bound) and which are masked per column (below some column's bound).  Stages
+// wholly below the block's smallest bound are never loaded: the key splits
+// are cut from the stages at or above it.  A column (or split) left with no
+// visible key ends with l = 0 and a finite m <= -1e29: weight 0 in any merge.
+template <int D, int NSUB, int NWAVE, bool KV8, bool SC = false, bool WIN = false>
 __device__ __forceinline__ void prefill_attn_block(
     const uint16_t* __restrict__ q, const void* __restrict__ kc, const void* __restrict__ vc,
     const void* __restrict__ pk, const void* __restrict__ pv, uint16_t* __restrict__ out,
     float* __restrict__ part_o, float* __restrict__ part_ml, int T, int start, int P, int Hkv, int G, int ldk,
     int kh, int sp, int ct, int nsplit, float sl2, const int32_t* __restrict__ plen, long prs, long pss,
-    PfScale<SC> ss = {}) {
+    PfScale<SC> ss = {}, PfWin<WIN> win = {}) {
     static_assert(KV8 || !SC, "scaled caches are fp8");
     constexpr int KS = D / 16;  // k-steps of the QK product
     constexpr int DT = D / 32;  // 32-row d tiles of the PV product
@@ -122,16 +144,33 @@ __device__ __forceinline__ void prefill_attn_block(
         kend = start + (min(NC, c0 + COLS) - 1) / G + 1;  // keys [0, kend) are visible to the block
     }
     const int nst_all = (kend + kPfKeys - 1) / kPfKeys;
-    // split-K: this block's stages [st0, st1) of the column tile's key range
-    const int per = (nst_all + nsplit - 1) / nsplit;
-    const int st0 = min(nst_all, sp * per), st1 = min(nst_all, st0 + per);
     // the wave index through readfirstlane: every per-unit bound below is then
     // provably wave-uniform, so the tile-skip and mask decisions compile to
     // scalar branches instead of exec-mask save/restore sequences
     const int lane = threadIdx.x & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const int r = lane & 31, h = lane >> 5;
+    // WIN: the first stage any column of the block sees a key of
+    int stlo = 0;
+    if constexpr (WIN) {
+        int blo;
+        if (prefix_mode) {  // the smallest bound over the block's rows (every wave computes it: no LDS hop)
+            blo = kend;
+            for (int c = c0 + lane; c < min(NC, c0 + COLS); c += kWave)
+                blo = min(blo, max(0, min(win.seq_len[c / G], ldk) - win.window));
+#pragma unroll
+            for (int msk = 1; msk < kWave; msk <<= 1) blo = min(blo, __shfl_xor(blo, msk, kWave));
+            blo = __builtin_amdgcn_readfirstlane(blo);
+        } else {
+            blo = start + c0 / G - win.window + 1;  // the first column's: positions grow with the column
+        }
+        stlo = min(nst_all, max(0, blo) / kPfKeys);
+    }
+    // split-K: this block's stages [st0, st1) of the column tile's key range
+    const int per = (nst_all - stlo + nsplit - 1) / nsplit;
+    const int st0 = min(nst_all, stlo + sp * per), st1 = min(nst_all, st0 + per);
 
     int qpos[NSUB], qmin[NSUB], qmax[NSUB], cf[NSUB];
+    int qlo[WIN ? NSUB : 1], lomin[WIN ? NSUB : 1], lomax[WIN ? NSUB : 1];
     bool uact[NSUB];
     bf16x8_t qf[NSUB][KS];
     f32x16_t o[NSUB][DT];
@@ -146,6 +185,17 @@ __device__ __forceinline__ void prefill_attn_block(
         const int c = min(cf[u] + r, NC - 1);  // padding lanes repeat the last column; results discarded
         const int t = c / G, g = c - t * G;
         qpos[u] = start + t;
+        if constexpr (WIN) {
+            qlo[u] = prefix_mode ? max(0, min(win.seq_len[t], ldk) - win.window) : qpos[u] - win.window + 1;
+            int lo = qlo[u], hi = qlo[u];
+#pragma unroll
+            for (int msk = 1; msk < kWave; msk <<= 1) {
+                lo = min(lo, __shfl_xor(lo, msk, kWave));
+                hi = max(hi, __shfl_xor(hi, msk, kWave));
+            }
+            lomin[u] = __builtin_amdgcn_readfirstlane(lo);
+            lomax[u] = __builtin_amdgcn_readfirstlane(hi);
+        }
         const uint16_t* qp = q + ((size_t)t * Hq + (size_t)kh * G + g) * D + 8 * h;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -241,6 +291,7 @@ __device__ __forceinline__ void prefill_attn_block(
 #pragma unroll
             for (int u = 0; u < NSUB; ++u) {
                 act[u] = uact[u] && kb <= qmax[u];
+                if constexpr (WIN) act[u] = act[u] && kb + 31 >= lomin[u];  // else wholly below every column's bound
                 any |= act[u];
             }
             if (!any) continue;  // wave-uniform
@@ -269,11 +320,15 @@ __device__ __forceinline__ void prefill_attn_block(
                 float mt = -1e30f;
                 // mask: the tile straddles some query's position (causal) or
                 // the end of the visible keys (prefix mode: no causal bound)
-                if (kb + 31 > qmin[u] || kb + 32 > kend) {
+                bool edge = kb + 31 > qmin[u] || kb + 32 > kend;
+                if constexpr (WIN) edge = edge || kb < lomax[u];  // ... or some column's window bound
+                if (edge) {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
                         const int key = kb + (i & 3) + 8 * (i >> 2) + 4 * h;
-                        s[u][i] = (key <= qpos[u] && key < kend) ? s[u][i] : -INFINITY;
+                        bool vis = key <= qpos[u] && key < kend;
+                        if constexpr (WIN) vis = vis && key >= qlo[u];
+                        s[u][i] = vis ? s[u][i] : -INFINITY;
                         mt = fmaxf(mt, s[u][i]);
                     }
                 } else {
@@ -383,6 +438,24 @@ __global__ __launch_bounds__(NWAVE * 64) void prefill_attn_kernel(
                                                 sp, ct, nsplit, sl2, plen, prs, pss, ss);
 }
 
+// prefill_attn_kernel under a sliding window (also the decode step's prefix
+// mode under one): its own kernels, so the full-attention ones keep their
+// arguments, code and registers.
+template <int D, int NSUB, int NWAVE, bool KV8, bool SC = false>
+__global__ __launch_bounds__(NWAVE * 64) void prefill_attn_win_kernel(
+    const uint16_t* __restrict__ q, const void* __restrict__ kc, const void* __restrict__ vc,
+    const void* __restrict__ pk, const void* __restrict__ pv, uint16_t* __restrict__ out,
+    float* __restrict__ part_o, float* __restrict__ part_ml, int T, int start, int P, int Hkv, int G, int ldk,
+    int ctiles, int nsplit, float sl2, const int32_t* __restrict__ plen, long prs, long pss, PfScale<SC> ss,
+    PfWin<true> win) {
+    const int kh = blockIdx.x % Hkv;
+    const int rest = (int)(blockIdx.x / Hkv);
+    const int sp = rest % nsplit;
+    const int ct = ctiles - 1 - rest / nsplit;  // heavy (late) column tiles first
+    prefill_attn_block<D, NSUB, NWAVE, KV8, SC, true>(q, kc, vc, pk, pv, out, part_o, part_ml, T, start, P, Hkv, G, ldk,
+                                                      kh, sp, ct, nsplit, sl2, plen, prs, pss, ss, win);
+}
+
 // Packed multi-sequence prefill (the engine's batched admission): q / out
 // [Ttot, Hq, D] hold every sequence's tokens back to back; block b runs work
 // item b / Hkv of the host-built table (sequence, column tile), sorted by
@@ -415,6 +488,35 @@ __global__ __launch_bounds__(NWAVE * 64) void prefill_varlen_kernel(
     prefill_attn_block<D, NSUB, NWAVE, KV8, SC>(q + row0, kc, vc, P > 0 ? pk : kc, P > 0 ? pv : vc, out + row0, nullptr,
                                                 nullptr, T, start, P, Hkv, G, ldk, kh, 0, ct, 1, sl2, nullptr, 1L, 1L,
                                                 ss);
+}
+
+// prefill_varlen_kernel under a sliding window
+template <int D, int NSUB, int NWAVE, bool KV8, bool SC = false>
+__global__ __launch_bounds__(NWAVE * 64) void prefill_varlen_win_kernel(
+    const uint16_t* __restrict__ q, const void* __restrict__ kcache, const void* __restrict__ vcache,
+    const void* __restrict__ pk, const void* __restrict__ pv, uint16_t* __restrict__ out,
+    const int32_t* __restrict__ items, const int32_t* __restrict__ seq, int Hkv, int G, int ldk, size_t slot_elems,
+    float sl2, PfScale<SC> ss, PfWin<true> win) {
+    const int kh = blockIdx.x % Hkv;
+    const int it = blockIdx.x / Hkv;
+    const int si = items[2 * it], ct = items[2 * it + 1];
+    const int off = seq[5 * si], T = seq[5 * si + 1], start = seq[5 * si + 2], slot = seq[5 * si + 3];
+    const int P = seq[5 * si + 4];
+    const size_t row0 = (size_t)off * Hkv * G * D;
+    const size_t kvoff = (size_t)slot * slot_elems * (KV8 ? 1 : 2);
+    const void* kc = static_cast<const char*>(kcache) + kvoff;
+    const void* vc = static_cast<const char*>(vcache) + kvoff;
+    if constexpr (SC) {
+        ss.k += (size_t)slot * Hkv * ldk;
+        ss.v += (size_t)slot * Hkv * ldk;
+        if (P <= 0) {
+            ss.pk = ss.k;
+            ss.pv = ss.v;
+        }
+    }
+    prefill_attn_block<D, NSUB, NWAVE, KV8, SC, true>(q + row0, kc, vc, P > 0 ? pk : kc, P > 0 ? pv : vc, out + row0,
+                                                      nullptr, nullptr, T, start, P, Hkv, G, ldk, kh, 0, ct, 1, sl2,
+                                                      nullptr, 1L, 1L, ss, win);
 }
 
 // split-K merge: out[row, :] = sum_s O_s exp2(m_s - M) / sum_s l_s exp2(m_s - M),
@@ -464,7 +566,61 @@ hipError_t launch_prefill(const uint16_t* q, const void* k, const void* v, const
     return hipGetLastError();
 }
 
+// launch_prefill under a sliding window
+template <int D, int NSUB, int NWAVE, bool KV8, bool SC = false>
+hipError_t launch_prefill_win(const uint16_t* q, const void* k, const void* v, const void* pk, const void* pv,
+                              uint16_t* out, float* po, float* pml, int T, int start, int P, int Hkv, int G, int ldk,
+                              int nsplit, float sl2, hipStream_t st, PfScale<SC> ss, int window) {
+    constexpr int COLS = 32 * NSUB * NWAVE;
+    const int ctiles = (T * G + COLS - 1) / COLS;
+    prefill_attn_win_kernel<D, NSUB, NWAVE, KV8, SC>
+        <<<dim3((unsigned)(ctiles * Hkv * nsplit)), NWAVE * kWave, 0, st>>>(
+            q, k, v, pk, pv, out, po, pml, T, start, P, Hkv, G, ldk, ctiles, nsplit, sl2, nullptr, 1L,
+            (long)T * G * Hkv, ss, PfWin<true>{window, nullptr});
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || nsplit == 1) return e;
+    const int rows = T * G * Hkv;
+    const size_t n = (size_t)rows * (D / 4);
+    prefill_combine_kernel<D><<<dim3((unsigned)((n + kBlock - 1) / kBlock)), kBlock, 0, st>>>(po, pml, out, rows,
+                                                                                             nsplit);
+    return hipGetLastError();
+}
+
 }  // namespace
+
+// dmcp_launch_prefix_partials / _scaled under a sliding window: row b's query
+// sits at position min(seq_len[b], ldk) - 1 and sees the prefix keys
+// [max(0, that + 1 - window), *plen); key tiles below every row's bound in the
+// query tile are skipped, boundary tiles masked per row, and a row whose bound
+// is at or past *plen writes empty partials (l = 0: weight 0 in the merge).
+// pks / pvs (both or neither): the per-row scaled prefix's exponent bytes.
+hipError_t dmcp_launch_prefix_partials_window(const uint16_t* q, const void* pk, const void* pv, const int32_t* plen,
+                                              float* part_o, float* part_ml, int B, int Hkv, int G, int D, int ldk,
+                                              int nsplit, int splits_total, float sl2, int kv8, const uint8_t* pks,
+                                              const uint8_t* pvs, const int32_t* seq_len, int window, hipStream_t st) {
+    constexpr int COLS = 32 * 4;
+    const int ctiles = (B * G + COLS - 1) / COLS;
+    const dim3 grid((unsigned)(ctiles * Hkv * nsplit));
+    if (!seq_len || window < 1 || (!pks != !pvs) || (pks && !kv8)) return hipErrorInvalidValue;
+    const PfWin<true> win{window, seq_len};
+#define DMCP_PFXW(DD, K8, SCL, SS)                                                                                 \
+    prefill_attn_win_kernel<DD, 1, 4, K8, SCL><<<grid, 4 * kWave, 0, st>>>(q, pk, pv, pk, pv, nullptr, part_o,       \
+                                                                          part_ml, B, ldk, 0, Hkv, G, ldk, ctiles, \
+                                                                          nsplit, sl2, plen, (long)splits_total,   \
+                                                                          1L, SS, win)
+    if (pks) {
+        const PfScale<true> ss{pks, pvs, pks, pvs};
+        if (D == 64) DMCP_PFXW(64, true, true, ss);
+        else if (D == 128) DMCP_PFXW(128, true, true, ss);
+        else return hipErrorInvalidValue;
+    } else if (D == 64 && kv8) DMCP_PFXW(64, true, false, PfScale<false>{});
+    else if (D == 64) DMCP_PFXW(64, false, false, PfScale<false>{});
+    else if (D == 128 && kv8) DMCP_PFXW(128, true, false, PfScale<false>{});
+    else if (D == 128) DMCP_PFXW(128, false, false, PfScale<false>{});
+    else return hipErrorInvalidValue;
+#undef DMCP_PFXW
+    return hipGetLastError();
+}
 
 // The decode step's shared-prefix attention on this kernel (called by
 // dmcp_decode_attention, dmcp_kernels.hip): q [B, Hq, D] (one query token per
@@ -655,6 +811,86 @@ int dmcp_prefill_varlen_scaled(const void* q, const void* kc, const void* vc, co
             (const uint16_t*)q, kc, vc, pk, pv, (uint16_t*)out, it, sq, Hkv, G, ldk, (size_t)slot_elems, sl2, ss);
     else
         return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// dmcp_prefill_attention / _scaled under a sliding window (window >= 1): query
+// t at position start + t sees keys (start + t - window, start + t].  One
+// entry point for the three cache formats: ks / vs (and pks / pvs with P > 0)
+// given = per-row scaled fp8, nullptr = bf16 (kv8 0) or unit-scale fp8 (kv8 1).
+int dmcp_prefill_attention_window(const void* q, const void* k, const void* v, const void* pk, const void* pv,
+                                  void* out, void* part_o, void* part_ml, int T, int start, int P, int Hq, int Hkv,
+                                  int D, int ldk, float scale, int variant, int nsplit, int kv8, void* stream,
+                                  const void* ks, const void* vs, const void* pks, const void* pvs, int window) {
+    if (T <= 0) return 0;
+    if (!q || !k || !v || !out || Hkv <= 0 || Hq % Hkv != 0 || start < 0 || P < 0 || P > start ||
+        start + T > ldk || (P > 0 && (!pk || !pv)) || nsplit < 1 || nsplit > 64 ||
+        (nsplit > 1 && (!part_o || !part_ml)) || window < 1 || (!ks != !vs) ||
+        (ks && (!kv8 || (P > 0 && (!pks || !pvs)))) || (variant != 0 && variant != 1))
+        return hipErrorInvalidValue;
+    if ((long)T * Hq > (1L << 28)) return hipErrorInvalidValue;
+    const int G = Hq / Hkv;
+    const float sl2 = scale * 1.4426950408889634f;
+    auto st = (hipStream_t)stream;
+    auto qq = (const uint16_t*)q;
+    const void* ppk = P > 0 ? pk : k;
+    const void* ppv = P > 0 ? pv : v;
+    auto oo = (uint16_t*)out;
+    auto po = (float*)part_o;
+    auto pml = (float*)part_ml;
+#define DMCP_PFW(DD, NW, K8, SCL, SS) \
+    launch_prefill_win<DD, 1, NW, K8, SCL>(qq, k, v, ppk, ppv, oo, po, pml, T, start, P, Hkv, G, ldk, nsplit, sl2, st, SS, \
+                                           window)
+#define DMCP_PFW_D(DD, NW)                                                        \
+    do {                                                                          \
+        if (ks) return DMCP_PFW(DD, NW, true, true, ss);                          \
+        if (kv8) return DMCP_PFW(DD, NW, true, false, PfScale<false>{});          \
+        return DMCP_PFW(DD, NW, false, false, PfScale<false>{});                  \
+    } while (0)
+    const PfScale<true> ss{(const uint8_t*)ks, (const uint8_t*)vs, (const uint8_t*)(P > 0 ? pks : ks),
+                           (const uint8_t*)(P > 0 ? pvs : vs)};
+    if (D == 64 && variant == 0) DMCP_PFW_D(64, 4);
+    if (D == 64 && variant == 1) DMCP_PFW_D(64, 8);
+    if (D == 128 && variant == 0) DMCP_PFW_D(128, 4);
+    if (D == 128 && variant == 1) DMCP_PFW_D(128, 8);
+#undef DMCP_PFW_D
+#undef DMCP_PFW
+    return hipErrorInvalidValue;
+}
+
+// dmcp_prefill_varlen / _scaled under a sliding window (window >= 1), the
+// formats selected as in dmcp_prefill_attention_window (ks / vs: the whole
+// exponent tables [S, Hkv, ldk]; pks / pvs: the prefix slot's rows of them)
+int dmcp_prefill_varlen_window(const void* q, const void* kc, const void* vc, const void* pk, const void* pv,
+                               void* out, const void* items, const void* seq, int nitems, int Hq, int Hkv, int D,
+                               int ldk, long slot_elems, float scale, int kv8, void* stream, const void* ks,
+                               const void* vs, const void* pks, const void* pvs, int window) {
+    if (nitems <= 0) return 0;
+    if (!q || !kc || !vc || !out || !items || !seq || Hkv <= 0 || Hq % Hkv != 0 ||
+        (long)nitems * Hkv > (1L << 31) || window < 1 || (!ks != !vs) ||
+        (ks && (!kv8 || (!pk != !pks) || (!pv != !pvs))))
+        return hipErrorInvalidValue;
+    const int G = Hq / Hkv;
+    const float sl2 = scale * 1.4426950408889634f;
+    const dim3 grid((unsigned)(nitems * Hkv));
+    auto st = (hipStream_t)stream;
+    auto it = (const int32_t*)items;
+    auto sq = (const int32_t*)seq;
+    const PfWin<true> win{window, nullptr};
+#define DMCP_PVW(DD, K8, SCL, SS)                                                                             \
+    prefill_varlen_win_kernel<DD, 1, 4, K8, SCL><<<grid, 4 * kWave, 0, st>>>(                                   \
+        (const uint16_t*)q, kc, vc, pk, pv, (uint16_t*)out, it, sq, Hkv, G, ldk, (size_t)slot_elems, sl2, SS, win)
+    if (ks) {
+        const PfScale<true> ss{(const uint8_t*)ks, (const uint8_t*)vs, (const uint8_t*)pks, (const uint8_t*)pvs};
+        if (D == 64) DMCP_PVW(64, true, true, ss);
+        else if (D == 128) DMCP_PVW(128, true, true, ss);
+        else return hipErrorInvalidValue;
+    } else if (D == 64 && kv8) DMCP_PVW(64, true, false, PfScale<false>{});
+    else if (D == 64) DMCP_PVW(64, false, false, PfScale<false>{});
+    else if (D == 128 && kv8) DMCP_PVW(128, true, false, PfScale<false>{});
+    else if (D == 128) DMCP_PVW(128, false, false, PfScale<false>{});
+    else return hipErrorInvalidValue;
+#undef DMCP_PVW
     return hipGetLastError();
 }
 

@@ -132,6 +132,15 @@ def lib() -> ctypes.CDLL:
                                                _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
             "dmcp_prefill_varlen_scaled": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_long,
                                             _f, _vp, _vp, _vp, _vp, _vp], _i),
+            # sliding-window attention (window=): one entry point per op for the three KV formats -- the unscaled
+            # sibling's list (kv8 kept), the nullable exponent tables (k, v, prefix k, v) behind the stream, then
+            # the window
+            "dmcp_decode_attention_window": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i,
+                                              _f, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i], _i),
+            "dmcp_prefill_attention_window": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f,
+                                               _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i], _i),
+            "dmcp_prefill_varlen_window": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_long,
+                                            _f, _i, _vp, _vp, _vp, _vp, _vp, _i], _i),
             "dmcp_kv_fork_scaled": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp], _i),
             # the routed expert MLP (csrc/moe.hip): h, router, ids, p, T, H, E, k, norm_topk
             "dmcp_moe_route": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
@@ -220,6 +229,16 @@ def _req_kv_scale(kv_scale: Optional[tuple], k_cache: torch.Tensor, name: str) -
             raise HipOpsError(f"{name}.{which}: shape {tuple(t.shape)} on {t.device}, the caches need "
                               f"{tuple(k_cache.shape[:-1])} on {k_cache.device}")
     return kv_scale[0], kv_scale[1]
+
+
+def _req_window(window, name: str) -> int:
+    """A sliding window, checked before any launch: an int >= 0 (None = 0 =
+    full attention, the unwindowed entry points)."""
+    if window is None:
+        return 0
+    if isinstance(window, bool) or not isinstance(window, int) or window < 0:
+        raise HipOpsError(f"{name}: window must be an integer >= 0 (0 = full attention), got {window!r}")
+    return int(window)
 
 
 def _req_out(t: torch.Tensor, dtype: torch.dtype, numel: int, name: str) -> None:
@@ -367,8 +386,15 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
                      seq_len: torch.Tensor, scale: float, workspace: Optional[tuple] = None,
                      chunk: int = 256, out: Optional[torch.Tensor] = None,
                      prefix: Optional["SharedPrefix"] = None, splits: Optional[int] = None,
-                     fork: Optional[torch.Tensor] = None, kv_scale: Optional[tuple] = None) -> torch.Tensor:
+                     fork: Optional[torch.Tensor] = None, kv_scale: Optional[tuple] = None,
+                     window: int = 0) -> torch.Tensor:
     """q [B, Hq, D]; caches [S, Hkv, MAXS, D]; slot/seq_len int32 [B].
+
+    ``window`` > 0 (sliding-window attention): a row of live length L attends
+    keys [max(0, L - window), L) of its logical sequence -- prefix, fork parent
+    and own keys alike; the per-row kernel covers [max(P, L - window), L) in
+    equal splits of that span and the prefix kernel masks each row's bound.
+    0: full attention, the unwindowed entry points.
 
     ``kv_scale`` (k_scale, v_scale uint8 [S, Hkv, MAXS]): the caches are
     per-row scaled fp8; a shared prefix then carries its slot's rows of the
@@ -394,6 +420,7 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     B, Hq, D = q.shape
     S, Hkv, MAXS, Dk = k_cache.shape
     _req(q, torch.bfloat16, "decode_attention.q")
+    window = _req_window(window, "decode_attention")
     kv8 = _req_kv(k_cache, v_cache, "decode_attention")
     kv_scale = _req_kv_scale(kv_scale, k_cache, "decode_attention")
     pks = pvs = None
@@ -452,6 +479,14 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
             raise HipOpsError("decode_attention: workspace too small")
     else:
         part_o = part_ml = None
+    if window:
+        ks, vs = kv_scale if kv_scale is not None else (None, None)
+        _check(lib().dmcp_decode_attention_window(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(slot), _ptr(seq_len),
+                                                  _ptr(out), _ptr(part_o), _ptr(part_ml), B, Hq, Hkv, D, MAXS, S,
+                                                  chunk, splits, float(scale), _ptr(pk), _ptr(pv), _ptr(plen), ps_max,
+                                                  kv8, _ptr(prows), _ptr(fork), _stream(), _ptr(ks), _ptr(vs),
+                                                  _ptr(pks), _ptr(pvs), window), "dmcp_decode_attention_window")
+        return out
     if kv_scale is not None:
         _check(lib().dmcp_decode_attention_scaled(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(slot), _ptr(seq_len),
                                                   _ptr(out), _ptr(part_o), _ptr(part_ml), B, Hq, Hkv, D, MAXS, S,
@@ -487,7 +522,7 @@ def prefill_splits(T: int, Hq: int, Hkv: int, variant: int = 0, target_blocks: i
 def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slot: int, start: int,
                       prefix_slot: Optional[int] = None, prefix_len: int = 0, scale: float = 1.0,
                       out: Optional[torch.Tensor] = None, variant: int = 0, nsplit: int = 0,
-                      kv_scale: Optional[tuple] = None) -> torch.Tensor:
+                      kv_scale: Optional[tuple] = None, window: int = 0) -> torch.Tensor:
     """Causal attention of q [T, Hq, D] (positions [start, start+T) of
     ``slot``, K/V already appended by rope_kv) over keys [0, start+T) of the
     caches [S, Hkv, MAXS, D]; keys [0, prefix_len) are read in place from
@@ -495,10 +530,14 @@ def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     kernel (csrc/prefill_attn.hip); ``nsplit`` > 1 splits every query tile's
     keys over that many blocks plus a merge kernel (0 = :func:`prefill_splits`).
     Returns [T, Hq, D] bf16.
-    ``kv_scale`` (k_scale, v_scale uint8 [S, Hkv, MAXS]): per-row scaled fp8 caches."""
+    ``kv_scale`` (k_scale, v_scale uint8 [S, Hkv, MAXS]): per-row scaled fp8 caches.
+    ``window`` > 0: the query at position i sees keys (i - window, i] only
+    (key tiles below a query tile's smallest bound are skipped, the key splits
+    cut from the rest); 0: full attention, the unwindowed entry points."""
     T, Hq, D = q.shape
     S, Hkv, MAXS, Dk = k_cache.shape
     _req(q, torch.bfloat16, "prefill_attention.q")
+    window = _req_window(window, "prefill_attention")
     kv8 = _req_kv(k_cache, v_cache, "prefill_attention")
     kv_scale = _req_kv_scale(kv_scale, k_cache, "prefill_attention")
     if Dk != D or v_cache.shape != k_cache.shape or not prefill_supported(Hq, Hkv, D):
@@ -523,6 +562,18 @@ def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     if nsplit > 1:
         part_o = torch.empty(nsplit * T * Hq * D, dtype=torch.float32, device=q.device)
         part_ml = torch.empty(nsplit * T * Hq * 2, dtype=torch.float32, device=q.device)
+    if window:
+        ks, vs = kv_scale if kv_scale is not None else (None, None)
+        scaled_prefix = kv_scale is not None and prefix_len
+        pks, pvs = (ks[int(prefix_slot)], vs[int(prefix_slot)]) if scaled_prefix else (None, None)
+        _check(lib().dmcp_prefill_attention_window(_ptr(q), _ptr(k_cache[slot]), _ptr(v_cache[slot]), _ptr(pk),
+                                                   _ptr(pv), _ptr(out), _ptr(part_o), _ptr(part_ml), T, start,
+                                                   prefix_len, Hq, Hkv, D, MAXS, float(scale), int(variant),
+                                                   int(nsplit), kv8, _stream(),
+                                                   _ptr(None if ks is None else ks[slot]),
+                                                   _ptr(None if vs is None else vs[slot]), _ptr(pks), _ptr(pvs),
+                                                   window), "dmcp_prefill_attention_window")
+        return out
     if kv_scale is not None:
         ks, vs = kv_scale
         pks, pvs = (ks[int(prefix_slot)], vs[int(prefix_slot)]) if prefix_len else (None, None)
@@ -583,17 +634,20 @@ def _varlen_meta(key: tuple, device) -> tuple:
 
 def prefill_attention_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, offsets, slots, starts,
                              prefix_slot: Optional[int] = None, prefix_lens=None, scale: float = 1.0,
-                             out: Optional[torch.Tensor] = None, kv_scale: Optional[tuple] = None) -> torch.Tensor:
+                             out: Optional[torch.Tensor] = None, kv_scale: Optional[tuple] = None,
+                             window: int = 0) -> torch.Tensor:
     """Packed multi-sequence prefill attention in ONE launch
     (csrc/prefill_attn.hip::prefill_varlen_kernel): q [Ttot, Hq, D], sequence
     i = rows [offsets[i], offsets[i+1]) at positions [starts[i], ...) of
     ``slots[i]``, its first ``prefix_lens[i]`` keys read in place from
     ``prefix_slot``.  Work items (sequence, 128-column tile) are ordered by
     descending key count on the host.  Returns [Ttot, Hq, D] bf16.
-    ``kv_scale`` (k_scale, v_scale uint8 [S, Hkv, MAXS]): per-row scaled fp8 caches."""
+    ``kv_scale`` (k_scale, v_scale uint8 [S, Hkv, MAXS]): per-row scaled fp8 caches.
+    ``window`` > 0: every sequence under the sliding window of :func:`prefill_attention`."""
     Ttot, Hq, D = q.shape
     S, Hkv, MAXS, Dk = k_cache.shape
     _req(q, torch.bfloat16, "prefill_attention_varlen.q")
+    window = _req_window(window, "prefill_attention_varlen")
     kv8 = _req_kv(k_cache, v_cache, "prefill_attention_varlen")
     kv_scale = _req_kv_scale(kv_scale, k_cache, "prefill_attention_varlen")
     if Dk != D or v_cache.shape != k_cache.shape or not prefill_supported(Hq, Hkv, D):
@@ -621,6 +675,15 @@ def prefill_attention_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: to
         pk, pv = k_cache[int(prefix_slot)], v_cache[int(prefix_slot)]
     else:
         pk = pv = None
+    if window:
+        ks, vs = kv_scale if kv_scale is not None else (None, None)
+        scaled_prefix = kv_scale is not None and any(plens)
+        pks, pvs = (ks[int(prefix_slot)], vs[int(prefix_slot)]) if scaled_prefix else (None, None)
+        _check(lib().dmcp_prefill_varlen_window(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(pk), _ptr(pv), _ptr(out),
+                                                _ptr(it_t), _ptr(seq_t), n_items, Hq, Hkv, D, MAXS, Hkv * MAXS * D,
+                                                float(scale), kv8, _stream(), _ptr(ks), _ptr(vs), _ptr(pks),
+                                                _ptr(pvs), window), "dmcp_prefill_varlen_window")
+        return out
     if kv_scale is not None:
         ks, vs = kv_scale
         pks, pvs = (ks[int(prefix_slot)], vs[int(prefix_slot)]) if any(plens) else (None, None)

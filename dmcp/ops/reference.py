@@ -301,17 +301,37 @@ class SharedPrefix(NamedTuple):
     v_scale: Optional[torch.Tensor] = None
 
 
+# ---- sliding-window attention.  A query at logical position i attends key j
+# iff j <= i and j > i - W: W keys including its own (the mask transformers
+# builds for Mistral / Qwen2).  Positions are the logical ones of the ops
+# below -- keys [0, P) from the shared prefix, keys up to the fork end from the
+# parent slot, the rest from the own slot -- and the window cuts that logical
+# sequence: where a key is stored does not matter.  ``window`` 0 (or None) is
+# full attention.  The cache stays linear; nothing is evicted.
+def window_arg(window, name: str = "window") -> int:
+    """``window`` validated: an int >= 0 (None = 0 = full attention); a
+    ValueError names the argument."""
+    if window is None:
+        return 0
+    if isinstance(window, bool) or not isinstance(window, int) or window < 0:
+        raise ValueError(f"{name} must be an integer >= 0 (0 = full attention), got {window!r}")
+    return int(window)
+
+
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slot: torch.Tensor,
                      seq_len: torch.Tensor, scale: float, workspace=None, chunk: int = 256,
                      out: Optional[torch.Tensor] = None, prefix: Optional[SharedPrefix] = None,
-                     fork: Optional[torch.Tensor] = None, kv_scale: Optional[tuple] = None) -> torch.Tensor:
-    """``fork`` [S, 2] (parent slot, end): keys below ``end`` of a row whose
+                     fork: Optional[torch.Tensor] = None, kv_scale: Optional[tuple] = None,
+                     window: int = 0) -> torch.Tensor:
+    """``window`` > 0: a row of live length L attends keys [max(0, L - window), L)
+    of its logical sequence only.  ``fork`` [S, 2] (parent slot, end): keys below ``end`` of a row whose
     slot has a parent come from the parent's slot (a method branch reading
     its class head's KV in place).  ``kv_scale`` (k_scale, v_scale): the caches
     are per-row scaled fp8; every key is decoded with the exponent byte of the
     slot it is read from (``prefix.k_scale`` / ``v_scale`` for the prefix)."""
     B, Hq, D = q.shape
     S, Hkv, MAXS, _ = k_cache.shape
+    window = window_arg(window, "decode_attention: window")
     ks, vs = _kv_scale_pair(kv_scale, k_cache, "decode_attention")
     if ks is not None and prefix is not None and (prefix.k_scale is None or prefix.v_scale is None):
         raise ValueError("decode_attention: a scaled cache's prefix needs k_scale / v_scale")
@@ -335,6 +355,8 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
             pre = (slice(None), slice(0, P))
             k = torch.cat([_kv_rows(prefix.k, prefix.k_scale if ks is not None else None, pre), k[:, P:]], dim=1)
             v = torch.cat([_kv_rows(prefix.v, prefix.v_scale if ks is not None else None, pre), v[:, P:]], dim=1)
+        if 0 < window < L:  # the last `window` keys of the logical sequence
+            k, v = k[:, L - window:], v[:, L - window:]
         qb = kv_float(q[b]).view(Hkv, G, D)
         att = torch.einsum("hgd,hld->hgl", qb, k) * scale
         p = torch.softmax(att, dim=-1)
@@ -349,12 +371,14 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
 def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slot: int, start: int,
                       prefix_slot: Optional[int] = None, prefix_len: int = 0, scale: float = 1.0,
                       out: Optional[torch.Tensor] = None, variant: int = 0, nsplit: int = 0,
-                      kv_scale: Optional[tuple] = None) -> torch.Tensor:
+                      kv_scale: Optional[tuple] = None, window: int = 0) -> torch.Tensor:
     """q [T, Hq, D] at positions [start, start+T) of ``slot``; every query
     sees the keys at or before its position.  Keys [0, prefix_len) come from
     ``prefix_slot``, the rest from ``slot``.  fp32 math, returns [T, Hq, D].
-    ``kv_scale`` (k_scale, v_scale): per-row scaled fp8 caches."""
+    ``kv_scale`` (k_scale, v_scale): per-row scaled fp8 caches.
+    ``window`` > 0: the query at position i sees keys (i - window, i] only."""
     T, Hq, D = q.shape
+    window = window_arg(window, "prefill_attention: window")
     Hkv = k_cache.shape[1]
     G = Hq // Hkv
     L = start + T
@@ -369,7 +393,10 @@ def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     qf = kv_float(q).view(T, Hkv, G, D)
     att = torch.einsum("thgd,hld->hgtl", qf, k) * scale  # [Hkv, G, T, L]
     pos = torch.arange(start, L, device=q.device)[:, None]
-    att = att.masked_fill(torch.arange(L, device=q.device)[None, :] > pos, float("-inf"))
+    keys = torch.arange(L, device=q.device)[None, :]
+    att = att.masked_fill(keys > pos, float("-inf"))
+    if window > 0:
+        att = att.masked_fill(keys <= pos - window, float("-inf"))
     y = torch.einsum("hgtl,hld->thgd", torch.softmax(att, dim=-1), v).reshape(T, Hq, D).to(q.dtype)
     if out is not None:
         out.copy_(y)
@@ -379,17 +406,19 @@ def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
 
 def prefill_attention_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, offsets, slots, starts,
                              prefix_slot: Optional[int] = None, prefix_lens=None, scale: float = 1.0,
-                             out: Optional[torch.Tensor] = None, kv_scale: Optional[tuple] = None) -> torch.Tensor:
+                             out: Optional[torch.Tensor] = None, kv_scale: Optional[tuple] = None,
+                             window: int = 0) -> torch.Tensor:
     """Several sequences' prefill in one packed q [Ttot, Hq, D]: sequence i
     is rows [offsets[i], offsets[i+1]) at positions [starts[i], ...) of
     ``slots[i]``, keys [0, prefix_lens[i]) read from ``prefix_slot``.
-    fp32 math per sequence (:func:`prefill_attention`)."""
+    fp32 math per sequence (:func:`prefill_attention`, ``window`` included)."""
+    window = window_arg(window, "prefill_attention_varlen: window")
     out = torch.empty_like(q) if out is None else out
     for i in range(len(slots)):
         a, b = int(offsets[i]), int(offsets[i + 1])
         P = int(prefix_lens[i]) if prefix_lens is not None else 0
         out[a:b] = prefill_attention(q[a:b], k_cache, v_cache, int(slots[i]), int(starts[i]),
-                                     prefix_slot if P else None, P, scale, kv_scale=kv_scale)
+                                     prefix_slot if P else None, P, scale, kv_scale=kv_scale, window=window)
     return out
 
 

@@ -442,7 +442,8 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
                      outliers=(7, 300, 1029, 1800), seed: int = 11, device: str = "cuda", rope_scaling=None,
                      qkv_bias: bool = False, model_type: Optional[str] = None, tie_embeddings: bool = False,
                      head_dim: Optional[int] = None, qk_norm: bool = False,
-                     chat_template: Optional[str] = None, k_bias_scale: float = 1.0) -> str:
+                     chat_template: Optional[str] = None, k_bias_scale: float = 1.0,
+                     sliding_window: Optional[int] = None, max_window_layers: Optional[int] = None) -> str:
     """A Llama-format checkpoint directory (``config.json``, one
     ``model.safetensors``, ``tokenizer.json``) with *trained-like* random
     weights -- no download exists here: heavy-tailed matrices (a Gaussian
@@ -464,7 +465,12 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
     ``k_norm`` weights [head_dim] drawn like the other norm weights (1 +- 0.25)
     after every other draw -- the Qwen3 layout; ``model_type="qwen3"`` writes
     the Qwen3 config keys (``head_dim``, ``layer_types``, ``attention_bias``,
-    ``use_sliding_window``, ``rope_theta`` 1e6).
+    ``use_sliding_window``, ``rope_theta`` 1e6).  ``model_type="mistral"``
+    writes the Mistral config keys over the Llama tensor layout.
+    ``sliding_window`` (config only, no tensor): Mistral's window over every
+    layer; with qwen2 / qwen3 it switches ``use_sliding_window`` on, the layers
+    ``i >= max_window_layers`` (default 0: all) taking it -- qwen3's
+    ``layer_types`` say the same per layer.
 
     ``chat_template``: a Jinja chat template (off by default: the files
     written without it are unchanged) for the ``tokenizer.json`` of ``root``
@@ -533,8 +539,18 @@ def llama_checkpoint(root: str, layers: int = 16, hidden: int = 2048, heads: int
         cfg.update({"model_type": "qwen3", "architectures": ["Qwen3ForCausalLM"], "hidden_act": "silu",
                     "head_dim": hd, "layer_types": ["full_attention"] * layers, "attention_bias": bool(qkv_bias),
                     "use_sliding_window": False, "attention_dropout": 0.0, "rope_theta": 1000000.0})
+    elif model_type == "mistral":
+        cfg.update({"model_type": "mistral", "architectures": ["MistralForCausalLM"], "hidden_act": "silu",
+                    "head_dim": hd, "sliding_window": sliding_window, "attention_dropout": 0.0})
     elif model_type is not None:
         cfg["model_type"] = model_type
+    if sliding_window is not None and model_type in ("qwen2", "qwen3"):
+        mwl = 0 if max_window_layers is None else int(max_window_layers)
+        cfg.update({"use_sliding_window": True, "sliding_window": int(sliding_window), "max_window_layers": mwl})
+        if model_type == "qwen3":
+            cfg["layer_types"] = ["sliding_attention" if i >= mwl else "full_attention" for i in range(layers)]
+    elif sliding_window is not None and model_type != "mistral":
+        raise ValueError("sliding_window needs model_type 'mistral', 'qwen2' or 'qwen3'")
     if qkv_bias and model_type not in ("qwen2", "qwen3"):
         cfg["attention_bias"] = True
     if head_dim is not None:
