@@ -40,10 +40,11 @@ MI355X mapping:
   (:class:`DecodeGraphs`), removing ~10 launches/layer of host overhead.
 
 Weights are random-initialised by default (no checkpoint on this host) or
-loaded from a Llama-, Qwen2-, Qwen3- or Qwen3-MoE-format safetensors directory
-(``load_safetensors``: RoPE scaling, q/k/v biases, Qwen3's per-head q/k
-RMSNorm and Qwen3-MoE's routed expert MLP -- ``ops.moe_mlp``, csrc/moe.hip, on
-every forward path -- included; a directory
+loaded from a Llama-, Qwen2-, Qwen3-, Qwen3-MoE- or GLM-4.5-format safetensors
+directory (``load_safetensors``: RoPE scaling, q/k/v biases, Qwen3's per-head q/k
+RMSNorm, Qwen3-MoE's routed expert MLP -- ``ops.moe_mlp``, csrc/moe.hip -- and
+GLM-4.5's sigmoid router with shared experts, leading dense layers and partial
+rotary embedding -- ``ops.moe_mlp_sh`` -- on every forward path; a directory
 it cannot reproduce is refused, ``check_checkpoint``).
 """
 from __future__ import annotations
@@ -120,6 +121,23 @@ class LMConfig:
     # as a block-scaled FP8 checkpoint stores them.  Set by the loader from the
     # checkpoint; a random-init preset with "fp8b" quantises its random experts
     moe_weight_dtype: str = "bf16"
+    # the router (ops.reference): "softmax" (Qwen3-MoE: top-k of the softmax) or
+    # "sigmoid" (GLM-4.5: the k largest of sigmoid + a per-expert selection
+    # bias w["l{i}.router_bias"], weighted by the unbiased scores, renormalised
+    # when norm_topk, then times moe_route_scale; ops.moe_mlp_sh).  moe_shared:
+    # always-on shared experts, a SwiGLU MLP of width moe_shared x
+    # moe_intermediate beside the routed ones (sigmoid router only).
+    # dense_lead: the first dense_lead layers keep the dense MLP of
+    # `intermediate`, the rest are routed.  The defaults are Qwen3-MoE's block
+    moe_score: str = "softmax"
+    moe_route_scale: float = 1.0
+    moe_shared: int = 0
+    dense_lead: int = 0
+    # partial rotary embedding: the width of a head that RoPE rotates (0 = the
+    # whole head).  The loader permutes each head's q / k rows so the kernels'
+    # whole-head rotation applies it (ops.reference.partial_rotary_perm); the
+    # cos / sin table holds cos 1, sin 0 for the pass-through pairs
+    rotary_dim: int = 0
     # sliding-window attention (Mistral; Qwen2 / Qwen3 with use_sliding_window):
     # one int per layer, the keys a query attends including its own (0 = every
     # key); None = full attention in every layer.  The loader resolves it from
@@ -131,12 +149,17 @@ class LMConfig:
     def qkv_dim(self) -> int:
         return (self.n_heads + 2 * self.n_kv_heads) * self.head_dim
 
+    def sparse_layer(self, i: int) -> bool:
+        """Layer i's MLP is the routed one (else the dense MLP of ``intermediate``)."""
+        return self.n_experts > 0 and i >= self.dense_lead
+
     def param_count(self) -> int:
-        mlp = (3 * self.intermediate * self.hidden if not self.n_experts
-               else self.n_experts * (3 * self.moe_intermediate + 1) * self.hidden)
-        per_layer = (self.qkv_dim * self.hidden + self.n_heads * self.head_dim * self.hidden
-                     + mlp + 2 * self.hidden)
-        return self.layers * per_layer + 2 * self.vocab_size * self.hidden + self.hidden
+        dense = 3 * self.intermediate * self.hidden
+        routed = ((self.n_experts + self.moe_shared) * 3 * self.moe_intermediate + self.n_experts) * self.hidden
+        n_sparse = max(0, self.layers - self.dense_lead) if self.n_experts else 0
+        per_layer = self.qkv_dim * self.hidden + self.n_heads * self.head_dim * self.hidden + 2 * self.hidden
+        return (self.layers * per_layer + n_sparse * routed + (self.layers - n_sparse) * dense
+                + 2 * self.vocab_size * self.hidden + self.hidden)
 
     @property
     def kv_elem_bytes(self) -> int:
@@ -222,10 +245,11 @@ class CheckpointUnsupported(ValueError):
     (:func:`check_checkpoint` gives the reason)."""
 
 
-SUPPORTED_MODEL_TYPES = ("llama", "qwen2", "qwen3", "qwen3_moe", "mistral")
+SUPPORTED_MODEL_TYPES = ("llama", "qwen2", "qwen3", "qwen3_moe", "mistral", "glm4_moe")
 SUPPORTED_ARCHITECTURES = ("LlamaForCausalLM", "Qwen2ForCausalLM", "Qwen3ForCausalLM", "Qwen3MoeForCausalLM",
-                           "MistralForCausalLM")
+                           "MistralForCausalLM", "Glm4MoeForCausalLM")
 MOE_ARCHITECTURE = "Qwen3MoeForCausalLM"
+GLM_MOE_ARCHITECTURE = "Glm4MoeForCausalLM"
 MISTRAL_ARCHITECTURE = "MistralForCausalLM"
 _LAYER_TYPES = ("full_attention", "sliding_attention")
 _DENSE_MLP = ("mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
@@ -335,6 +359,80 @@ def _moe_config(hf: dict) -> Tuple[Optional[tuple], Optional[str]]:
                       f"num_experts_per_tok {k} are outside the routed MLP kernels' contract (hidden and "
                       f"intermediate multiples of 64, hidden <= 8192, at most 256 experts)")
     return (ne, k, inter, bool(hf.get("norm_topk_prob", False))), None
+
+
+def _partial_rotary(hf: dict, head_dim: int) -> Tuple[Optional[int], Optional[str]]:
+    """(LMConfig.rotary_dim, None) of a ``glm4_moe`` config.json --
+    ``partial_rotary_factor`` at the top level or inside ``rope_parameters`` /
+    ``rope_scaling``; 0 for the whole head -- or (None, reason).  A config
+    without the key has the factor 0.5, as the checkpoint's own code assumes."""
+    f = hf.get("partial_rotary_factor")
+    for key in ("rope_parameters", "rope_scaling"):
+        d = hf.get(key)
+        if f is None and isinstance(d, dict):
+            f = d.get("partial_rotary_factor")
+    if f is None:
+        f = 0.5
+    if isinstance(f, bool) or not isinstance(f, (int, float)) or not math.isfinite(f):
+        return None, f"partial_rotary_factor {f!r} is not a number"
+    R = int(head_dim * f)
+    if not 0 < R <= head_dim or R % 2:
+        return None, (f"partial_rotary_factor {f!r} gives a rotary width of {R} for head_dim {head_dim} (it must "
+                      f"be even and in (0, head_dim])")
+    return (0 if R == head_dim else R), None
+
+
+def _glm_moe_config(hf: dict) -> Tuple[Optional[dict], Optional[str]]:
+    """The routed-MLP keys of a ``glm4_moe`` config.json as LMConfig fields
+    (n_experts, experts_per_tok, moe_intermediate, norm_topk, moe_score,
+    moe_route_scale, moe_shared, dense_lead) plus ``qk_norm`` and ``mtp`` (the
+    appended multi-token-prediction layers, which are not loaded), or (None,
+    reason) naming the key.  Absent keys take the values the checkpoint's own
+    code gives them."""
+    ne = hf.get("n_routed_experts", hf.get("num_experts", hf.get("num_local_experts")))
+    if isinstance(ne, bool) or not isinstance(ne, int) or ne <= 0:
+        return None, "model_type 'glm4_moe' needs n_routed_experts (a positive integer) in config.json"
+    k, inter = hf.get("num_experts_per_tok"), hf.get("moe_intermediate_size")
+    if isinstance(k, bool) or not isinstance(k, int) or k <= 0:
+        return None, "config.json: num_experts_per_tok is missing or not a positive integer"
+    if isinstance(inter, bool) or not isinstance(inter, int) or inter <= 0:
+        return None, "config.json: moe_intermediate_size is missing or not a positive integer"
+    if k > ne:
+        return None, f"num_experts_per_tok {k} exceeds n_routed_experts {ne}"
+    for key in ("n_group", "topk_group"):
+        if hf.get(key, 1) not in (1, None):
+            return None, (f"{key} {hf[key]!r} is not supported (only 1: group-limited routing is not implemented)")
+    S = hf.get("n_shared_experts", 1)
+    S = 0 if S is None else S
+    if isinstance(S, bool) or not isinstance(S, int) or S < 0:
+        return None, f"n_shared_experts {S!r} is not an integer >= 0"
+    layers = hf["num_hidden_layers"]
+    lead = hf.get("first_k_dense_replace", 1)
+    if isinstance(lead, bool) or not isinstance(lead, int) or not 0 <= lead <= layers:
+        return None, f"first_k_dense_replace {lead!r} is outside [0, num_hidden_layers {layers}]"
+    scale = hf.get("routed_scaling_factor", 1.0)
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not (math.isfinite(scale) and scale > 0):
+        return None, f"routed_scaling_factor {scale!r} is not a finite number > 0"
+    mtp = hf.get("num_nextn_predict_layers", 0)
+    mtp = 0 if mtp is None else mtp
+    if isinstance(mtp, bool) or not isinstance(mtp, int) or mtp < 0:
+        return None, f"num_nextn_predict_layers {mtp!r} is not an integer >= 0"
+    if hf.get("quantization_config") is not None:
+        return None, ("quantization_config is not supported for model_type 'glm4_moe' (the e4m3 expert GEMMs do not "
+                      "run under the sigmoid router with shared experts yet; load the bf16 checkpoint)")
+    if not ops.moe_sh_supported(hf["hidden_size"], inter, ne, k, S):
+        return None, (f"hidden_size {hf['hidden_size']} / moe_intermediate_size {inter} / n_routed_experts {ne} / "
+                      f"num_experts_per_tok {k} / n_shared_experts {S} are outside the routed MLP kernels' contract "
+                      f"(hidden and intermediate multiples of 64, hidden <= 8192, routed + shared experts <= 256, "
+                      f"at most 64 shared)")
+    return dict(n_experts=ne, experts_per_tok=k, moe_intermediate=inter, norm_topk=bool(hf.get("norm_topk_prob", True)),
+                moe_score="sigmoid", moe_route_scale=float(scale), moe_shared=S, dense_lead=lead,
+                qk_norm=bool(hf.get("use_qk_norm", False)), mtp=mtp), None
+
+
+_GLM_SHARED = ("mlp.shared_experts.gate_proj.weight", "mlp.shared_experts.up_proj.weight",
+               "mlp.shared_experts.down_proj.weight")
+_GLM_ROUTER_BIAS = "mlp.gate.e_score_correction_bias"
 
 
 # Block-scaled FP8 checkpoints (quantization_config.quant_method "fp8"): the
@@ -529,17 +627,27 @@ def check_checkpoint(path: str, chat_template: Optional[str] = "auto") -> Option
     kvh = hf.get("num_key_value_heads", heads)
     if not isinstance(kvh, int) or kvh <= 0 or heads % kvh:
         return f"num_attention_heads {heads} is not a multiple of num_key_value_heads {kvh}"
-    moe = None
+    moe = glm = None
     if mt == "qwen3_moe":
         moe, why = _moe_config(hf)
         if moe is None:
             return why
-    if archs and (MOE_ARCHITECTURE in archs) != (moe is not None):
+    if mt == "glm4_moe":
+        glm, why = _glm_moe_config(hf)
+        if glm is None:
+            return why
+        moe = (glm["n_experts"], glm["experts_per_tok"], glm["moe_intermediate"], glm["norm_topk"])
+    if archs and ((MOE_ARCHITECTURE in archs) != (mt == "qwen3_moe")
+                  or (GLM_MOE_ARCHITECTURE in archs) != (glm is not None)):
         return f"architectures {archs!r} does not match model_type {mt!r}"
-    qk_norm = mt in ("qwen3", "qwen3_moe")
+    qk_norm = mt in ("qwen3", "qwen3_moe") or bool(glm and glm["qk_norm"])
     head_dim = hf.get("head_dim") or hf["hidden_size"] // heads
     if qk_norm and head_dim not in QK_NORM_HEAD_DIMS:
         return f"head_dim {head_dim} is not supported with q_norm / k_norm (supported: 64, 128)"
+    if glm is not None:
+        _, why = _partial_rotary(hf, head_dim)
+        if why is not None:
+            return why
     try:
         _checkpoint_rope(hf)
     except (ValueError, TypeError) as e:
@@ -559,14 +667,25 @@ def check_checkpoint(path: str, chat_template: Optional[str] = "auto") -> Option
     # the scales are consumed with their tensors (checked above)
     names = [n for n in heads if not n.endswith(".weight" + _SCALE_SUFFIX)]
     layers = hf["num_hidden_layers"]
+    lead = glm["dense_lead"] if glm else 0
+    if glm and glm["mtp"]:
+        # the multi-token-prediction layers the hub files carry after the last
+        # decoder layer are not part of the model, and only those are skipped
+        mtp = tuple(f"model.layers.{i}." for i in range(layers, layers + glm["mtp"]))
+        names = [n for n in names if not n.startswith(mtp)]
     consumed = {"model.embed_tokens.weight", "model.norm.weight", "lm_head.weight"}
     required = {"model.embed_tokens.weight", "model.norm.weight"}
     for i in range(layers):
         p = f"model.layers.{i}."
-        required.update(p + n for n in _LAYER_TENSORS if moe is None or n not in _DENSE_MLP)
-        if moe is not None:
+        sparse = moe is not None and i >= lead
+        required.update(p + n for n in _LAYER_TENSORS if not sparse or n not in _DENSE_MLP)
+        if sparse:
             required.add(p + "mlp.gate.weight")
             required.update(f"{p}mlp.experts.{e}.{n}.weight" for e in range(moe[0]) for n in _EXPERT_PROJS)
+            if glm:
+                required.add(p + _GLM_ROUTER_BIAS)
+                if glm["moe_shared"]:
+                    required.update(p + n for n in _GLM_SHARED)
         consumed.update(p + n for n in _QKV_BIASES)
         if qk_norm:
             required.update(p + n for n in _QK_NORMS)
@@ -577,6 +696,9 @@ def check_checkpoint(path: str, chat_template: Optional[str] = "auto") -> Option
             continue
         if n.endswith((".o_proj.bias", ".gate_proj.bias", ".up_proj.bias", ".down_proj.bias")):
             return f"tensor {n} is not supported (only the q/k/v projections take a bias)"
+        if "shared_expert" in n and glm is not None:
+            return (f"tensor {n} is not supported (n_shared_experts is {glm['moe_shared']}: shared expert tensors "
+                    f"belong to the sparse layers of a checkpoint with n_shared_experts > 0)")
         if "shared_expert" in n:
             return f"tensor {n} is not supported (shared experts: only Qwen3-MoE's routed experts are loaded)"
         return f"tensor {n} is not consumed by the loader (a layout other than Llama / Qwen2 / Qwen3)"
@@ -609,12 +731,32 @@ def check_checkpoint(path: str, chat_template: Optional[str] = "auto") -> Option
             shapes = _checkpoint_tensor_shapes(path, tuple(want))
         except Exception as e:  # noqa: BLE001
             return f"safetensors of {path} cannot be read ({e})"
+        inter_d = hf["intermediate_size"]
+        dense = {"gate_proj.weight": ((inter_d, hidden), "intermediate_size, hidden_size"),
+                 "up_proj.weight": ((inter_d, hidden), "intermediate_size, hidden_size"),
+                 "down_proj.weight": ((hidden, inter_d), "hidden_size, intermediate_size")}
+        S = glm["moe_shared"] if glm else 0
+        shared = {"gate_proj.weight": ((S * inter, hidden), "n_shared_experts x moe_intermediate_size, hidden_size"),
+                  "up_proj.weight": ((S * inter, hidden), "n_shared_experts x moe_intermediate_size, hidden_size"),
+                  "down_proj.weight": ((hidden, S * inter), "hidden_size, n_shared_experts x moe_intermediate_size")}
         for n in sorted(shapes):
-            if ".mlp." not in n:
+            if ".mlp." not in n or n not in consumed:
                 continue
-            exp, keys = next(v for s, v in want.items() if n.endswith(s))
+            table = want
+            if ".mlp.shared_experts." in n:
+                table = shared
+            elif ".mlp.experts." not in n and not n.endswith("mlp.gate.weight"):
+                table = dense  # a lead layer's dense MLP
+            exp, keys = next(v for s, v in table.items() if n.endswith(s))
             if shapes[n] != exp:
                 return f"tensor {n} has shape {list(shapes[n])}, expected {list(exp)} ({keys})"
+        if glm:
+            for i in range(lead, layers):
+                n = f"model.layers.{i}.{_GLM_ROUTER_BIAS}"
+                if heads[n][1] != (n_exp,):
+                    return f"tensor {n} has shape {list(heads[n][1])}, expected [{n_exp}] (n_routed_experts)"
+                if heads[n][0] not in ("F32", "BF16", "F16"):
+                    return f"tensor {n} has dtype {heads[n][0]}, expected F32"
         # the experts are stored in one format: the stacked device tensors hold one
         f8 = [n for n in sorted(shapes) if ".mlp.experts." in n and heads[n][0] == "F8_E4M3"]
         plain = [n for n in sorted(shapes) if ".mlp.experts." in n and heads[n][0] != "F8_E4M3"]
@@ -752,7 +894,32 @@ class LocalLM:
         # rows, then its up rows), w["l{i}.we_down"] [E, H, I], all bf16
         # -- or, moe_weight_dtype "fp8b", w["l{i}.we_gu8"] / w["l{i}.we_down8"] in e4m3 with the block scales
         # w["l{i}.we_gu_s"] [E, 2 ceil(I / 128), ceil(H / 128)] / w["l{i}.we_down_s"] [E, ceil(H / 128), ceil(I / 128)]
+        # -- under moe_score "sigmoid" (GLM-4.5) also w["l{i}.router_bias"] fp32 [E], and we_gu / we_down stack
+        # E + moe_shared experts: the routed ones, then the shared MLP's slices (ops.reference.moe_stack_shared).
+        # Layers below dense_lead hold the dense MLP's w["l{i}.wgu"] / w["l{i}.wdown"] instead
         self.moe = cfg.n_experts > 0
+        if cfg.moe_score not in ("softmax", "sigmoid"):
+            raise ValueError(f"moe_score must be 'softmax' or 'sigmoid', got {cfg.moe_score!r}")
+        self.moe_sig = self.moe and cfg.moe_score == "sigmoid"
+        if not self.moe_sig and (cfg.moe_shared or cfg.moe_route_scale != 1.0):
+            raise ValueError(f"{cfg.name}: moe_shared {cfg.moe_shared} / moe_route_scale {cfg.moe_route_scale} need "
+                             f"n_experts > 0 and moe_score 'sigmoid'")
+        if (isinstance(cfg.moe_shared, bool) or not isinstance(cfg.moe_shared, int) or cfg.moe_shared < 0
+                or not (math.isfinite(cfg.moe_route_scale) and cfg.moe_route_scale > 0)):
+            raise ValueError(f"{cfg.name}: moe_shared must be an integer >= 0 and moe_route_scale finite and > 0, got "
+                             f"{cfg.moe_shared!r} / {cfg.moe_route_scale!r}")
+        if not isinstance(cfg.dense_lead, int) or not 0 <= cfg.dense_lead <= cfg.layers or (cfg.dense_lead
+                                                                                              and not self.moe):
+            raise ValueError(f"{cfg.name}: dense_lead {cfg.dense_lead!r} must be in [0, layers {cfg.layers}] and needs "
+                             f"n_experts > 0")
+        try:
+            ops.reference.rotary_dim_arg(cfg.head_dim, cfg.rotary_dim)
+        except ValueError as e:
+            raise ValueError(f"{cfg.name}: {e}") from None
+        if cfg.rotary_dim and "fp8" in (cfg.prefill_dtype, cfg.decode_dtype):
+            raise ValueError(f"{cfg.name}: rotary_dim {cfg.rotary_dim} (partial rotary) is not applied by the MXFP8 "
+                             f"GEMMs' weights: use prefill_dtype / decode_dtype 'bf16', got prefill_dtype="
+                             f"{cfg.prefill_dtype!r} decode_dtype={cfg.decode_dtype!r}")
         if cfg.moe_weight_dtype not in ("bf16", "fp8b"):
             raise ValueError(f"moe_weight_dtype must be 'bf16' or 'fp8b', got {cfg.moe_weight_dtype!r}")
         self.moe_w8 = self.moe and cfg.moe_weight_dtype == "fp8b"
@@ -765,16 +932,26 @@ class LocalLM:
             if not 1 <= cfg.experts_per_tok <= cfg.n_experts:
                 raise ValueError(f"{cfg.name}: experts_per_tok {cfg.experts_per_tok} outside [1, n_experts "
                                  f"{cfg.n_experts}]")
-            if torch.device(device).type == "cuda" and not ops.moe_supported(cfg.hidden, cfg.moe_intermediate,
-                                                                             cfg.n_experts, cfg.experts_per_tok):
+            if torch.device(device).type == "cuda" and not (
+                    ops.moe_sh_supported(cfg.hidden, cfg.moe_intermediate, cfg.n_experts, cfg.experts_per_tok,
+                                         cfg.moe_shared) if self.moe_sig else
+                    ops.moe_supported(cfg.hidden, cfg.moe_intermediate, cfg.n_experts, cfg.experts_per_tok)):
                 raise ValueError(f"{cfg.name}: hidden {cfg.hidden} / moe_intermediate {cfg.moe_intermediate} / "
-                                 f"n_experts {cfg.n_experts} / experts_per_tok {cfg.experts_per_tok} are outside "
-                                 f"the routed MLP kernels' contract (ops.moe_supported)")
-            if "l0.router" not in self.w:
-                raise ValueError(f"{cfg.name}: n_experts {cfg.n_experts} but the weights hold no l0.router")
-            if ("l0.we_gu8" in self.w) != self.moe_w8:
-                raise ValueError(f"{cfg.name}: moe_weight_dtype {cfg.moe_weight_dtype!r} does not match the weights "
-                                 f"({'l0.we_gu8' if 'l0.we_gu8' in self.w else 'l0.we_gu'})")
+                                 f"n_experts {cfg.n_experts} / experts_per_tok {cfg.experts_per_tok}"
+                                 + (f" / moe_shared {cfg.moe_shared}" if self.moe_sig else "") + " are outside "
+                                 f"the routed MLP kernels' contract (ops.moe_supported"
+                                 + (" / ops.moe_sh_supported)" if self.moe_sig else ")"))
+            if self.moe_sig and self.moe_w8:
+                raise ValueError(f"{cfg.name}: moe_weight_dtype 'fp8b' has no kernel under moe_score 'sigmoid'")
+            s0 = cfg.dense_lead  # the first routed layer
+            if s0 < cfg.layers:
+                if f"l{s0}.router" not in self.w:
+                    raise ValueError(f"{cfg.name}: n_experts {cfg.n_experts} but the weights hold no l{s0}.router")
+                if (f"l{s0}.we_gu8" in self.w) != self.moe_w8:
+                    raise ValueError(f"{cfg.name}: moe_weight_dtype {cfg.moe_weight_dtype!r} does not match the "
+                                     f"weights ({f'l{s0}.we_gu8' if f'l{s0}.we_gu8' in self.w else f'l{s0}.we_gu'})")
+                if self.moe_sig and f"l{s0}.router_bias" not in self.w:
+                    raise ValueError(f"{cfg.name}: moe_score 'sigmoid' but the weights hold no l{s0}.router_bias")
         # sliding windows: _wkw(i) is layer i's extra attention keyword -- empty
         # for a full-attention layer, so such layers (and whole models) make
         # the calls they always made and never reach a windowed entry point
@@ -792,8 +969,11 @@ class LocalLM:
         self.moe_rows = self.moe_ws = None
         if self.moe:
             self.moe_rows = max(1, min(max(max(c.max_batch, c.max_rows), self.MOE_PREFILL_ROWS),
-                                       ops.MOE_MAX_PAIRS // c.experts_per_tok))
-            if torch.device(device).type == "cuda":
+                                       ops.MOE_MAX_PAIRS // (c.experts_per_tok + c.moe_shared)))
+            if torch.device(device).type == "cuda" and self.moe_sig:
+                self.moe_ws = ops.moe_sh_workspace(self.moe_rows, c.hidden, c.moe_intermediate, c.n_experts,
+                                                   c.experts_per_tok, c.moe_shared, self.device)
+            elif torch.device(device).type == "cuda":
                 self.moe_ws = ops.moe_workspace(self.moe_rows, c.hidden, c.moe_intermediate, c.n_experts,
                                                 c.experts_per_tok, self.device)
         self.shared_prefix = shared_prefix
@@ -814,7 +994,8 @@ class LocalLM:
             self.v_scale = torch.full(kv_shape[:-1], 127, dtype=torch.uint8, device=self.device)
         # (a QK-norm model's table is built in fp32 like its own code's: ops.reference.rope_tables)
         self.cos_sin = ops.rope_tables(c.max_seq, c.head_dim, c.rope_theta, device=self.device,
-                                       scaling=c.rope_scaling, fp32_angles=self.has_qk_norm).contiguous()
+                                       scaling=c.rope_scaling, fp32_angles=self.has_qk_norm,
+                                       rotary_dim=c.rotary_dim).contiguous()
         self.scale = 1.0 / math.sqrt(c.head_dim)
         self.max_rows = max(c.max_batch, c.max_rows)
         # method branches: per slot (parent slot, end) -- the decode attention
@@ -977,10 +1158,13 @@ class LocalLM:
             w[f"l{i}.ln2"] = ones(c.hidden)
             w[f"l{i}.wqkv"] = rnd(c.qkv_dim, c.hidden)
             w[f"l{i}.wo"] = rnd(c.hidden, c.n_heads * c.head_dim, std=out_std)
-            if c.n_experts:
+            if c.sparse_layer(i):
                 w[f"l{i}.router"] = rnd(c.n_experts, c.hidden)
-                gu = rnd(c.n_experts, 2 * c.moe_intermediate, c.hidden)
-                down = rnd(c.n_experts, c.hidden, c.moe_intermediate, std=out_std)
+                n_stack = c.n_experts + c.moe_shared  # the shared slices ride behind the routed experts
+                gu = rnd(n_stack, 2 * c.moe_intermediate, c.hidden)
+                down = rnd(n_stack, c.hidden, c.moe_intermediate, std=out_std)
+                if c.moe_score == "sigmoid":  # a selection bias large enough to change selections
+                    w[f"l{i}.router_bias"] = rnd(c.n_experts, std=0.25).float()
                 if c.moe_weight_dtype == "fp8b":  # the same draws, quantised as a block-scaled checkpoint's are
                     inter = c.moe_intermediate
                     g8, gs = ops.block_fp8_quant(gu[:, :inter])
@@ -1005,7 +1189,7 @@ class LocalLM:
         pairs = [("norm_f", "lm_head")]
         for i in range(c.layers):
             pairs += [(f"l{i}.ln1", f"l{i}.wqkv")]
-            if not c.n_experts:  # a routed MLP keeps ln2: the router and every expert read the normalised row
+            if not c.sparse_layer(i):  # a routed MLP keeps ln2: the router and every expert read the normalised row
                 pairs += [(f"l{i}.ln2", f"l{i}.wgu")]
         if not hasattr(self, "norm_g"):
             # the checkpoint's own norm weights: the MXFP8 paths normalise
@@ -1038,10 +1222,12 @@ class LocalLM:
 
     @classmethod
     def load_safetensors(cls, path: str, device: str = "cuda", **cfg_overrides) -> "LocalLM":
-        """Loads a Llama-, Qwen2- or Qwen3-format checkpoint directory
-        (config.json + *.safetensors) as the model it is: RoPE scaling
-        ("linear", "llama3"), q/k/v projection biases and Qwen3's per-head
-        q/k RMSNorm included.  A block-scaled FP8 checkpoint keeps its experts
+        """Loads a Llama-, Qwen2-, Qwen3-, Mistral- or GLM-4.5-format checkpoint
+        directory (config.json + *.safetensors) as the model it is: RoPE scaling
+        ("linear", "llama3"), q/k/v projection biases, per-head q/k RMSNorm,
+        the routed expert MLPs (Qwen3-MoE's softmax router; GLM-4.5's sigmoid
+        router with its selection bias, shared experts, leading dense layers
+        and partial rotary embedding) included.  A block-scaled FP8 checkpoint keeps its experts
         in e4m3 (``moe_weight_dtype`` "fp8b") and has every other F8 projection
         dequantised to bf16 here.  A directory the loader cannot
         reproduce raises :class:`CheckpointUnsupported` with the reason
@@ -1063,6 +1249,15 @@ class LocalLM:
         moe = _moe_config(hf)[0] if hf.get("model_type") == "qwen3_moe" else None
         if moe is not None:
             cfg = replace(cfg, n_experts=moe[0], experts_per_tok=moe[1], moe_intermediate=moe[2], norm_topk=moe[3])
+        glm = _glm_moe_config(hf)[0] if hf.get("model_type") == "glm4_moe" else None
+        perm = None  # partial rotary: each q / k head's rows in the whole-head rotation's order
+        if glm is not None:
+            moe = (glm["n_experts"], glm["experts_per_tok"], glm["moe_intermediate"], glm["norm_topk"])
+            cfg = replace(cfg, rotary_dim=_partial_rotary(hf, cfg.head_dim)[0],
+                          **{k: v for k, v in glm.items() if k not in ("qk_norm", "mtp")})
+            if cfg.rotary_dim:
+                perm = ops.reference.partial_rotary_perm(cfg.head_dim, cfg.rotary_dim)
+        qk_norm = hf.get("model_type") in ("qwen3", "qwen3_moe") or bool(glm and glm["qk_norm"])
         cfg = replace(cfg, **cfg_overrides)
         if "layer_windows" not in cfg_overrides:  # against the slots' capacity, overrides applied
             cfg = replace(cfg, layer_windows=resolve_windows(checkpoint_windows(hf)[0], cfg.max_seq))
@@ -1091,10 +1286,17 @@ class LocalLM:
                     return ops.block_fp8_dequant(t.to(dev), raw[k + _SCALE_SUFFIX].to(dev), torch.bfloat16).contiguous()
                 return t.to(dtype=torch.bfloat16, device=dev).contiguous()
 
-            experts_f8 = (moe is not None and fp8
+            experts_f8 = (moe is not None and fp8 and glm is None
                           and raw["model.layers.0.mlp.experts.0.gate_proj.weight"].dtype == torch.float8_e4m3fn)
             if experts_f8:
                 cfg = replace(cfg, moe_weight_dtype="fp8b")
+
+            def heads_perm(t, n):
+                """``t`` [n x head_dim, ...] with each head's rows permuted for the partial rotary."""
+                if perm is None:
+                    return t
+                idx = (torch.arange(n)[:, None] * cfg.head_dim + perm[None, :]).reshape(-1).to(t.device)
+                return t.index_select(0, idx).contiguous()
 
             w = {"embed": g("model.embed_tokens.weight"), "norm_f": g("model.norm.weight"),
                  "lm_head": g("lm_head.weight") if "lm_head.weight" in raw else g("model.embed_tokens.weight")}
@@ -1102,21 +1304,32 @@ class LocalLM:
                 p = f"model.layers.{i}."
                 w[f"l{i}.ln1"] = g(p + "input_layernorm.weight")
                 w[f"l{i}.ln2"] = g(p + "post_attention_layernorm.weight")
-                w[f"l{i}.wqkv"] = torch.cat([g(p + "self_attn.q_proj.weight"), g(p + "self_attn.k_proj.weight"),
+                w[f"l{i}.wqkv"] = torch.cat([heads_perm(g(p + "self_attn.q_proj.weight"), cfg.n_heads),
+                                             heads_perm(g(p + "self_attn.k_proj.weight"), cfg.n_kv_heads),
                                              g(p + "self_attn.v_proj.weight")], 0).contiguous()
                 if p + "self_attn.q_proj.bias" in raw:  # Qwen2: q/k/v biases, stacked like wqkv
-                    w[f"l{i}.bqkv"] = torch.cat([g(p + "self_attn.q_proj.bias"), g(p + "self_attn.k_proj.bias"),
+                    w[f"l{i}.bqkv"] = torch.cat([heads_perm(g(p + "self_attn.q_proj.bias"), cfg.n_heads),
+                                                 heads_perm(g(p + "self_attn.k_proj.bias"), cfg.n_kv_heads),
                                                  g(p + "self_attn.v_proj.bias")], 0).contiguous()
-                if hf.get("model_type") in ("qwen3", "qwen3_moe"):  # per-head q / k RMSNorm weights [head_dim]
-                    w[f"l{i}.qnorm"] = g(p + "self_attn.q_norm.weight")
-                    w[f"l{i}.knorm"] = g(p + "self_attn.k_norm.weight")
+                if qk_norm:  # per-head q / k RMSNorm weights [head_dim]
+                    w[f"l{i}.qnorm"] = heads_perm(g(p + "self_attn.q_norm.weight"), 1)
+                    w[f"l{i}.knorm"] = heads_perm(g(p + "self_attn.k_norm.weight"), 1)
                 w[f"l{i}.wo"] = g(p + "self_attn.o_proj.weight")
-                if moe is not None:
+                if moe is not None and i >= cfg.dense_lead:
                     E, _, inter, _ = moe
+                    S = cfg.moe_shared
                     w[f"l{i}.router"] = g(p + "mlp.gate.weight")
+                    if glm is not None:  # the selection bias stays fp32
+                        w[f"l{i}.router_bias"] = raw[p + _GLM_ROUTER_BIAS].to(dtype=torch.float32,
+                                                                              device=dev).contiguous()
                     wdt = torch.float8_e4m3fn if experts_f8 else torch.bfloat16
-                    gu = torch.empty((E, 2 * inter, cfg.hidden), dtype=wdt, device=dev)
-                    down = torch.empty((E, cfg.hidden, inter), dtype=wdt, device=dev)
+                    gu = torch.empty((E + S, 2 * inter, cfg.hidden), dtype=wdt, device=dev)
+                    down = torch.empty((E + S, cfg.hidden, inter), dtype=wdt, device=dev)
+                    if S:  # the shared MLP's slices behind the routed experts (ops.reference.moe_stack_shared)
+                        q = f"{p}mlp.shared_experts."
+                        gu[E:, :inter].copy_(raw[q + "gate_proj.weight"].view(S, inter, cfg.hidden))
+                        gu[E:, inter:].copy_(raw[q + "up_proj.weight"].view(S, inter, cfg.hidden))
+                        down[E:].copy_(raw[q + "down_proj.weight"].view(cfg.hidden, S, inter).permute(1, 0, 2))
                     if experts_f8:  # the e4m3 bytes as they are, and their block scales beside them
                         nbi, nbh = -(-inter // FP8_BLOCK), -(-cfg.hidden // FP8_BLOCK)
                         gu_s = torch.empty((E, 2 * nbi, nbh), dtype=torch.float32, device=dev)
@@ -1175,7 +1388,11 @@ class LocalLM:
         combine).  More rows than the workspace holds go in chunks."""
         c = self.cfg
         w = self.w
-        if self.moe_w8:  # block-scaled e4m3 experts: the same launches over half the weight bytes
+        if self.moe_sig:  # the sigmoid router, the shared slices stacked behind the routed experts
+            op = ops.moe_mlp_sh
+            args = (w[f"l{i}.router"], w[f"l{i}.router_bias"], w[f"l{i}.we_gu"], w[f"l{i}.we_down"],
+                    c.experts_per_tok, c.norm_topk, c.moe_route_scale, c.moe_shared)
+        elif self.moe_w8:  # block-scaled e4m3 experts: the same launches over half the weight bytes
             op = ops.moe_mlp_w8
             args = (w[f"l{i}.router"], w[f"l{i}.we_gu8"], w[f"l{i}.we_gu_s"], w[f"l{i}.we_down8"],
                     w[f"l{i}.we_down_s"], c.experts_per_tok, c.norm_topk)
@@ -1194,7 +1411,7 @@ class LocalLM:
 
     def _mlp_norm(self, i: int, h: torch.Tensor, resid: torch.Tensor, nxt: torch.Tensor) -> torch.Tensor:
         """Layer i's MLP (dense or routed) + residual + the next RMSNorm."""
-        if self.moe:
+        if self.cfg.sparse_layer(i):
             return self._moe(i, h, resid, nxt)
         return ops.add_rmsnorm(self._mlp(i, h), nxt, self.cfg.eps, residual=resid)
 
@@ -1426,7 +1643,7 @@ class LocalLM:
                 h = ops.wgemm_resid_norm(att, self.w[f"l{i}.wo"], resid, self.w[f"l{i}.ln2"], c.eps, self.wgemm_ws)
             else:
                 h = ops.add_rmsnorm(F.linear(att, self.w[f"l{i}.wo"]), self.w[f"l{i}.ln2"], c.eps, residual=resid)
-            if self.moe:
+            if c.sparse_layer(i):
                 h = self._moe(i, h, resid, nxt)
             elif mlp_t:
                 act = ops.tgemm_swiglu(h, self.w[f"l{i}.wgu"])
@@ -1526,7 +1743,7 @@ class LocalLM:
                                        prefix=self._prefix(i, prefix_rows), splits=splits, kv_scale=kvs,
                                        **self._wkw(i))
             ops.fused_resid(att.view(B, c.n_heads * c.head_dim), self.w[f"l{i}.wo"], r)
-            if self.moe:
+            if c.sparse_layer(i):
                 # the norm fused_swiglu folds into its prologue, explicit: the
                 # router and every chosen expert read the same normalised row
                 self._moe(i, ops.add_rmsnorm(r, self.w[f"l{i}.ln2"], c.eps), r, None)
@@ -1831,7 +2048,12 @@ class LocalLM:
             o = torch.einsum("hts,shd->thd", torch.softmax(att, -1), v).reshape(T, -1)
             x = x + o @ w[f"l{i}.wo"].t()
             h = rms(x, w[f"l{i}.ln2"])
-            if self.moe:
+            if self.moe_sig and c.sparse_layer(i):
+                x = x + ops.reference.moe_mlp_sh_math(h, w[f"l{i}.router"], w[f"l{i}.router_bias"], w[f"l{i}.we_gu"],
+                                                      w[f"l{i}.we_down"], c.experts_per_tok, c.norm_topk,
+                                                      c.moe_route_scale, c.moe_shared)
+                continue
+            if c.sparse_layer(i):
                 if self.moe_w8:  # the experts dequantised exactly (fp32), one layer at a time
                     we_gu, we_down = ops.reference.moe_w8_dequant(self.w[f"l{i}.we_gu8"], self.w[f"l{i}.we_gu_s"],
                                                                   self.w[f"l{i}.we_down8"], self.w[f"l{i}.we_down_s"])

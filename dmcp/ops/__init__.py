@@ -20,7 +20,7 @@ from .hip import (PGEMM_TILE_N, WMX_MAX_ROWS, pgemm_supported, wgemm_mx_resid_no
                   wgemm_mx_swiglu, wmx_plan)
 from .hip import (TGEMM_MAX_ROWS, tgemm, tgemm_lm_head_argmax, tgemm_lm_head_sample,  # noqa: F401
                   tgemm_resid_norm, tgemm_rope_kv, tgemm_swiglu, wgemm)
-from .hip import MOE_MAX_PAIRS, moe_supported, moe_workspace  # noqa: F401
+from .hip import MOE_MAX_PAIRS, moe_sh_supported, moe_sh_workspace, moe_supported, moe_workspace  # noqa: F401
 from .reference import Penalty, penalize  # noqa: F401
 from .reference import SharedPrefix, mx_dequant, quantize_weight, rope_tables, weight_dequant  # noqa: F401
 from .reference import block_fp8_dequant, block_fp8_quant  # noqa: F401
@@ -62,8 +62,8 @@ DEVICE_OPS = ("history_mark", "history_reset",
               "mx_quant", "rmsnorm_mx", "pgemm", "pgemm_resid", "pgemm_swiglu", "pgemm_qkv", "fused_rope_kv",
               "wgemm_rope_kv", "tgemm_rope_kv",
               # the routed expert MLP of a mixture-of-experts layer (csrc/moe.hip), over bf16 and over
-              # block-scaled FP8 expert weights
-              "moe_route", "moe_mlp", "moe_mlp_w8")
+              # block-scaled FP8 expert weights; and under the sigmoid router with shared experts (GLM-4.5)
+              "moe_route", "moe_mlp", "moe_mlp_w8", "moe_route_sig", "moe_mlp_sh")
 for _name in DEVICE_OPS:
     globals()[_name] = _by_device(_name)
 del _name

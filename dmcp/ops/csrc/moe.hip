@@ -42,6 +42,16 @@
 // block's scale is applied to that fp32 partial sum (acc += s * part), never
 // to a weight.  Everything else -- activations, routing, grouping, combine --
 // is bf16 / fp32 as above.
+//
+// Sigmoid routing with shared experts (dmcp_moe_route_sig / dmcp_moe_mlp_sh;
+// GLM-4.5, defined in dmcp/ops/reference.py, moe_route_sig_math): step 1 is
+// moe_route_sig_kernel -- sigmoid scores, an fp32 bias added for the selection
+// only, the unbiased scores renormalised over the k routed ranks and scaled --
+// and a shared MLP of width S I rides along as S pseudo-experts E .. E + S - 1
+// that every row chooses with weight 1 (a SwiGLU MLP is a sum over slices of
+// its intermediate dimension).  Steps 2-6 are the same kernels over E + S
+// groups and k + S pairs per row: a shared slice is one group holding all T
+// rows, a dense GEMM on the same kernel body.
 #include "dmcp_common.hpp"
 
 namespace {
@@ -141,6 +151,112 @@ __global__ __launch_bounds__(kBlock) void moe_route_kernel(const uint16_t* __res
     for (int s = 0; s < kEPL; ++s) {
         const int j = s * kWave + lane;
         if (j < k) p[(size_t)t * k + j] = sel[s] / den;
+    }
+}
+
+// ------------------------------------------- 1b. route, sigmoid scores (GLM-4.5)
+// The router of GLM-4.5 / DeepSeek-V3-style blocks with one expert group
+// (dmcp/ops/reference.py, moe_route_sig_math): s = sigmoid(h . Wr^T); the k
+// largest of s + bias (bias fp32 [E], for the selection only; ties to the
+// lower id) are chosen; their weights are the unbiased s, divided by
+// (sum + 1e-20) when `norm`, then multiplied by `scale`.  A row has k + S
+// pairs: after the k routed ones come the S shared pseudo-experts
+// (E + s, 1.0), which the grouping and the GEMMs treat as experts E .. E + S - 1
+// that every row chooses.
+__global__ __launch_bounds__(kBlock) void moe_route_sig_kernel(const uint16_t* __restrict__ h,
+                                                               const uint16_t* __restrict__ wr,
+                                                               const float* __restrict__ bias,
+                                                               int32_t* __restrict__ ids, float* __restrict__ p, int T,
+                                                               int H, int E, int k, int S, int norm, float scale) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int t = blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
+    if (t >= T) return;  // whole waves leave; no block-level barrier below
+    const uint4* hr = reinterpret_cast<const uint4*>(h + (size_t)t * H);
+    const int nvec = H >> 3;
+    const int kk = k + S;
+    // expert e lives in lane e % 64, slot e / 64: its score sg and its
+    // selection score sc = sg + bias (-inf: no such expert, or a NaN logit)
+    float sg[kEPL], sc[kEPL];
+#pragma unroll
+    for (int s = 0; s < kEPL; ++s) {
+        sg[s] = 0.f;
+        sc[s] = -INFINITY;
+    }
+    for (int e = 0; e < E; ++e) {
+        const uint4* we = reinterpret_cast<const uint4*>(wr + (size_t)e * H);
+        float acc = 0.f;
+        for (int v = lane; v < nvec; v += kWave) {
+            float a[8], b[8];
+            unpack8(hr[v], a);
+            unpack8(we[v], b);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc = fmaf(a[j], b[j], acc);
+        }
+        acc = wave_sum(acc);
+        const bool ok = acc == acc;  // a NaN logit never wins, and never blocks the selection
+        const float sig = ok ? 1.f / (1.f + expf(-acc)) : 0.f;
+        float sel = ok ? sig + bias[e] : -INFINITY;
+        if (!(sel == sel)) sel = -INFINITY;
+#pragma unroll
+        for (int s = 0; s < kEPL; ++s)
+            if ((e >> 6) == s && (e & 63) == lane) {
+                sg[s] = sig;
+                sc[s] = sel;
+            }
+    }
+    // k rounds of arg-max over the experts not taken yet, as in
+    // moe_route_kernel: the largest selection score, the lowest id among equals
+    uint32_t taken = 0u;
+    float sel[kEPL];  // rank j's weight in lane j % 64, slot j / 64
+#pragma unroll
+    for (int s = 0; s < kEPL; ++s) sel[s] = 0.f;
+    for (int j = 0; j < k; ++j) {
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int s = 0; s < kEPL; ++s) {
+            const int e = s * kWave + lane;
+            if (e < E && !((taken >> s) & 1u)) {
+                const float v = sc[s];
+                if (v > bv || (v == bv && e < bi)) { bv = v; bi = e; }
+            }
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const float ov = __shfl_xor(bv, m, kWave);
+            const int oi = __shfl_xor(bi, m, kWave);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        bi = min(max(bi, 0), E - 1);
+        if ((bi & 63) == lane) taken |= 1u << (bi >> 6);
+        if (lane == 0) ids[(size_t)t * kk + j] = bi;
+        // the chosen expert's unbiased score, from the lane that holds it
+        float mine = 0.f;
+#pragma unroll
+        for (int s = 0; s < kEPL; ++s)
+            if ((bi >> 6) == s) mine = sg[s];
+        const float wj = __shfl(mine, bi & 63, kWave);
+#pragma unroll
+        for (int s = 0; s < kEPL; ++s)
+            if ((j >> 6) == s && (j & 63) == lane) sel[s] = wj;
+    }
+    float den = 1.f;
+    if (norm) {
+        // a butterfly sum: equal scores (k a power of two) add up exactly,
+        // so the weights come out as exactly scale / k
+        float sacc = 0.f;
+#pragma unroll
+        for (int s = 0; s < kEPL; ++s) sacc += sel[s];
+        den = wave_sum(sacc) + 1e-20f;
+    }
+#pragma unroll
+    for (int s = 0; s < kEPL; ++s) {
+        const int j = s * kWave + lane;
+        if (j < k) p[(size_t)t * kk + j] = sel[s] / den * scale;
+    }
+    if (lane < S) {  // S <= 64 (moe_sh_shape_ok)
+        ids[(size_t)t * kk + k + lane] = E + lane;
+        p[(size_t)t * kk + k + lane] = 1.f;
     }
 }
 
@@ -524,6 +640,12 @@ bool moe_shape_ok(int T, int H, int I, int E, int k, int MT) {
            k >= 1 && k <= E && (MT == 32 || MT == 128) && (long long)T * k < (1ll << 30);
 }
 
+// The sigmoid-routed block with S shared pseudo-experts: the same contract
+// over E + S groups and k + S pairs per row; scale finite is the caller's.
+bool moe_sh_shape_ok(int T, int H, int I, int E, int k, int S, int MT) {
+    return E >= 1 && k >= 1 && k <= E && S >= 0 && S <= 64 && moe_shape_ok(T, H, I, E + S, k + S, MT);
+}
+
 template <int RT, typename WT>
 void launch_gemms(const uint16_t* h, const WT* wgu, const float* sgu, const WT* wdown, const float* sdown,
                   const int32_t* perm, const int32_t* tiles, const int32_t* ntiles, uint16_t* act, float* y, int P,
@@ -536,21 +658,34 @@ void launch_gemms(const uint16_t* h, const WT* wgu, const float* sgu, const WT* 
 
 // The six launches of dmcp_moe_mlp / dmcp_moe_mlp_w8 (WT: the expert weights'
 // element; sgu / sdown: the e4m3 form's block scales, null for bf16).
+//
+// sig: the sigmoid router (moe_route_sig_kernel) with its selection bias,
+// weight scale and S shared pseudo-experts; wgu / wdown then stack E + S
+// experts, a row has k + S pairs, and every later stage runs over E + S groups
+// and k + S pairs per row exactly as it does over E and k.
 template <typename WT>
 int moe_mlp_launch(const void* h, const void* wr, const void* wgu, const void* sgu, const void* wdown,
                    const void* sdown, void* ids, void* p, void* cnt, void* offs, void* perm, void* tiles, void* ntiles,
-                   void* act, void* y, void* residual, const void* norm_w, void* out, int T, int H, int I, int E, int k,
-                   int norm, int MT, float eps, void* stream) {
-    if (!moe_shape_ok(T, H, I, E, k, MT)) return (int)hipErrorInvalidValue;
+                   void* act, void* y, void* residual, const void* norm_w, void* out, int T, int H, int I, int E_r,
+                   int k_r, int norm, int MT, float eps, void* stream, bool sig = false, const void* bias = nullptr,
+                   float scale = 1.f, int S = 0) {
+    if (sig ? !moe_sh_shape_ok(T, H, I, E_r, k_r, S, MT) || !bias : !moe_shape_ok(T, H, I, E_r, k_r, MT))
+        return (int)hipErrorInvalidValue;
     if (!norm_w && !residual && !out) return (int)hipErrorInvalidValue;
     if (norm_w && !out) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
+    const int E = E_r + S, k = k_r + S;  // groups, pairs per row
     const int P = T * k;
     const int max_tiles = (P + MT - 1) / MT + E;
     if (max_tiles > 65535) return (int)hipErrorInvalidValue;  // grid.y
     const int wpb = kBlock / kWave;
-    moe_route_kernel<<<(T + wpb - 1) / wpb, kBlock, 0, st>>>((const uint16_t*)h, (const uint16_t*)wr, (int32_t*)ids,
-                                                             (float*)p, T, H, E, k, norm);
+    if (sig)
+        moe_route_sig_kernel<<<(T + wpb - 1) / wpb, kBlock, 0, st>>>((const uint16_t*)h, (const uint16_t*)wr,
+                                                                     (const float*)bias, (int32_t*)ids, (float*)p, T,
+                                                                     H, E_r, k_r, S, norm, scale);
+    else
+        moe_route_kernel<<<(T + wpb - 1) / wpb, kBlock, 0, st>>>((const uint16_t*)h, (const uint16_t*)wr,
+                                                                 (int32_t*)ids, (float*)p, T, H, E, k, norm);
     moe_count_kernel<<<E, kWave, 0, st>>>((const int32_t*)ids, (int32_t*)cnt, P);
     moe_scatter_kernel<<<E, kWave, 0, st>>>((const int32_t*)ids, (const int32_t*)cnt, (int32_t*)offs, (int32_t*)perm,
                                             (int32_t*)tiles, (int32_t*)ntiles, P, E, MT, max_tiles);
@@ -613,6 +748,38 @@ int dmcp_moe_mlp_w8(const void* h, const void* wr, const void* wgu8, const void*
     if (!wgu8 || !sgu || !wdown8 || !sdown) return (int)hipErrorInvalidValue;
     return moe_mlp_launch<uint8_t>(h, wr, wgu8, sgu, wdown8, sdown, ids, p, cnt, offs, perm, tiles, ntiles, act, y,
                                    residual, norm_w, out, T, H, I, E, k, norm, MT, eps, stream);
+}
+
+// The sigmoid router alone (GLM-4.5; one expert group): bias fp32 [E] enters
+// the selection only, the weights are the unbiased scores, renormalised over
+// the k routed ones when norm, then times scale.  ids int32 / p fp32
+// [T, k + S]: the last S pairs of a row are the shared pseudo-experts
+// (E + s, 1.0).
+int dmcp_moe_route_sig(const void* h, const void* wr, const void* bias, void* ids, void* p, int T, int H, int E, int k,
+                       int S, int norm, float scale, void* stream) {
+    if (!bias || !moe_sh_shape_ok(T, H, 64, E, k, S, 32) || !(scale > 0.f) || scale > 3.0e38f)
+        return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const int wpb = kBlock / kWave;
+    moe_route_sig_kernel<<<(T + wpb - 1) / wpb, kBlock, 0, st>>>((const uint16_t*)h, (const uint16_t*)wr,
+                                                                 (const float*)bias, (int32_t*)ids, (float*)p, T, H, E,
+                                                                 k, S, norm, scale);
+    return (int)hipGetLastError();
+}
+
+// dmcp_moe_mlp under the sigmoid router with S shared experts as
+// pseudo-experts E .. E + S - 1: wgu [E + S, 2 I, H], wdown [E + S, H, I] (the
+// shared MLP of width S I cut into S slices of width I), and every workspace
+// part sized with k + S for k and E + S for E.  The combine adds the k routed
+// ranks in rank order, then the S shared slices in order (weight 1).
+int dmcp_moe_mlp_sh(const void* h, const void* wr, const void* bias, const void* wgu, const void* wdown, void* ids,
+                    void* p, void* cnt, void* offs, void* perm, void* tiles, void* ntiles, void* act, void* y,
+                    void* residual, const void* norm_w, void* out, int T, int H, int I, int E, int k, int S, int norm,
+                    float scale, int MT, float eps, void* stream) {
+    if (!(scale > 0.f) || scale > 3.0e38f) return (int)hipErrorInvalidValue;
+    return moe_mlp_launch<uint16_t>(h, wr, wgu, nullptr, wdown, nullptr, ids, p, cnt, offs, perm, tiles, ntiles, act,
+                                    y, residual, norm_w, out, T, H, I, E, k, norm, MT, eps, stream, true, bias, scale,
+                                    S);
 }
 
 }  // extern "C"

@@ -149,6 +149,11 @@ def lib() -> ctypes.CDLL:
             "dmcp_moe_mlp": ([_vp] * 16 + [_i, _i, _i, _i, _i, _i, _i, _f, _vp], _i),
             # the same over block-scaled e4m3 experts: h, router, w_gu8, s_gu, w_down8, s_down, then as above
             "dmcp_moe_mlp_w8": ([_vp] * 18 + [_i, _i, _i, _i, _i, _i, _i, _f, _vp], _i),
+            # the sigmoid router (GLM-4.5): h, router, bias, ids, p, T, H, E, k, S, norm_topk, route_scale
+            "dmcp_moe_route_sig": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp], _i),
+            # h, router, bias, w_gu, w_down (E + S stacked), the 9 workspace parts, residual, norm_w, out,
+            # T, H, I, E, k, S, norm_topk, route_scale, row tile, eps
+            "dmcp_moe_mlp_sh": ([_vp] * 17 + [_i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _vp], _i),
         }
         for name, (args, res) in sigs.items():
             try:
@@ -2104,6 +2109,27 @@ def moe_workspace(rows: int, hidden: int, inter: int, n_experts: int, top_k: int
     return torch.empty(_moe_layout(rows, hidden, inter, n_experts, top_k)[1], dtype=torch.uint8, device=device)
 
 
+def moe_sh_supported(hidden: int, inter: int, n_experts: int, top_k: int, n_shared: int = 0) -> bool:
+    """The contract of the sigmoid-routed MLP with ``n_shared`` shared
+    pseudo-experts (:func:`moe_mlp_sh`): :func:`moe_supported` over E + S
+    groups and k + S pairs per row (so E + S <= 256), at most 64 shared slices
+    (the routing wave writes them with one lane each)."""
+    return (isinstance(n_shared, int) and 0 <= n_shared <= 64 and 1 <= top_k <= n_experts
+            and moe_supported(hidden, inter, n_experts + n_shared, top_k + n_shared))
+
+
+def moe_sh_workspace(rows: int, hidden: int, inter: int, n_experts: int, top_k: int, n_shared: int,
+                     device) -> torch.Tensor:
+    """The scratch of :func:`moe_mlp_sh` for launches of up to ``rows`` rows:
+    :func:`moe_workspace`'s parts sized for k + S pairs per row and E + S groups."""
+    if (not moe_sh_supported(hidden, inter, n_experts, top_k, n_shared) or rows <= 0
+            or rows * (top_k + n_shared) > MOE_MAX_PAIRS):
+        raise HipOpsError(f"moe_sh_workspace: unsupported shape (rows {rows}, hidden {hidden}, inter {inter}, "
+                          f"experts {n_experts}, top_k {top_k}, shared {n_shared})")
+    return torch.empty(_moe_layout(rows, hidden, inter, n_experts + n_shared, top_k + n_shared)[1], dtype=torch.uint8,
+                       device=device)
+
+
 def _moe_args(h, w_router, w_gu, w_down, top_k, name) -> tuple:
     _req(h, torch.bfloat16, f"{name}.h")
     _req(w_router, torch.bfloat16, f"{name}.w_router")
@@ -2155,11 +2181,15 @@ def moe_mlp(h: torch.Tensor, w_router: torch.Tensor, w_gu: torch.Tensor, w_down:
                     workspace, out)
 
 
-def _moe_run(name, h, w_router, weights, T, H, inter, E, top_k, norm_topk, residual, norm_w, eps, workspace, out):
-    """The checks on workspace, residual, norm and out shared by :func:`moe_mlp`
-    and :func:`moe_mlp_w8`, all before the launch; ``weights``: the tensors
-    between the router and the workspace parts of ``dmcp_<name>``."""
-    offs, need = _moe_layout(max(T, 1), H, inter, E, top_k)
+def _moe_run(name, h, w_router, weights, T, H, inter, E, top_k, norm_topk, residual, norm_w, eps, workspace, out,
+             shared=None):
+    """The checks on workspace, residual, norm and out shared by :func:`moe_mlp`,
+    :func:`moe_mlp_w8` and :func:`moe_mlp_sh`, all before the launch;
+    ``weights``: the tensors between the router and the workspace parts of
+    ``dmcp_<name>``.  ``shared``: (n_shared, route_scale) of the sigmoid-routed
+    op, whose workspace and row tile count k + S pairs per row and E + S groups."""
+    S = shared[0] if shared else 0
+    offs, need = _moe_layout(max(T, 1), H, inter, E + S, top_k + S)
     if workspace is None:
         workspace = torch.empty(need, dtype=torch.uint8, device=h.device)
     _req(workspace, torch.uint8, f"{name}.workspace")
@@ -2184,6 +2214,12 @@ def _moe_run(name, h, w_router, weights, T, H, inter, E, top_k, norm_topk, resid
         if base % 16:
             raise HipOpsError(f"{name}: workspace must be 16-byte aligned")
         parts = [ctypes.c_void_p(base + o) for o in offs]
+        if shared:
+            _check(lib().dmcp_moe_mlp_sh(_ptr(h), _ptr(w_router), *[_ptr(t) for t in weights], *parts,
+                                         _ptr(residual), _ptr(norm_w), _ptr(out), T, H, inter, E, top_k, S,
+                                         int(bool(norm_topk)), float(shared[1]), moe_row_tile(T, E + S, top_k + S),
+                                         float(eps), _stream()), f"dmcp_{name}")
+            return out if out is not None else residual
         _check(getattr(lib(), f"dmcp_{name}")(_ptr(h), _ptr(w_router), *[_ptr(t) for t in weights], *parts,
                                               _ptr(residual), _ptr(norm_w), _ptr(out), T, H, inter, E, top_k,
                                               int(bool(norm_topk)), moe_row_tile(T, E, top_k), float(eps),
@@ -2242,3 +2278,79 @@ def moe_mlp_w8(h: torch.Tensor, w_router: torch.Tensor, w_gu8: torch.Tensor, s_g
             raise HipOpsError(f"{name}.{which}: must be 16-byte aligned")
     return _moe_run(name, h, w_router, (w_gu8, s_gu, w_down8, s_down), T, H, inter, E, top_k, norm_topk, residual,
                     norm_w, eps, workspace, out)
+
+
+def _moe_sh_args(h, w_router, bias, w_gu, w_down, top_k, route_scale, n_shared, name) -> tuple:
+    """The argument checks of the sigmoid-routed ops, all before any launch."""
+    _req(h, torch.bfloat16, f"{name}.h")
+    _req(w_router, torch.bfloat16, f"{name}.w_router")
+    if h.dim() != 2 or w_router.dim() != 2 or h.shape[1] != w_router.shape[1]:
+        raise HipOpsError(f"{name}: h {tuple(h.shape)} does not match the router {tuple(w_router.shape)}")
+    T, H = h.shape
+    E = w_router.shape[0]
+    if not isinstance(bias, torch.Tensor):
+        raise HipOpsError(f"{name}.bias: expected a tensor")
+    _req(bias, torch.float32, f"{name}.bias")
+    if tuple(bias.shape) != (E,) or bias.device != h.device:
+        raise HipOpsError(f"{name}.bias: shape {tuple(bias.shape)} on {bias.device}, the router needs ({E},) on "
+                          f"{h.device}")
+    if isinstance(n_shared, bool) or not isinstance(n_shared, int) or n_shared < 0:
+        raise HipOpsError(f"{name}: n_shared {n_shared!r} must be an integer >= 0")
+    if isinstance(route_scale, bool) or not isinstance(route_scale, (int, float)) \
+            or not (math.isfinite(route_scale) and 0 < route_scale <= 3.0e38):
+        raise HipOpsError(f"{name}: route_scale {route_scale!r} must be finite and > 0")
+    inter = 64
+    if w_gu is not None:
+        _req(w_gu, torch.bfloat16, f"{name}.w_gu")
+        _req(w_down, torch.bfloat16, f"{name}.w_down")
+        inter = w_down.shape[2] if w_down.dim() == 3 else -1
+        G = E + n_shared
+        if tuple(w_gu.shape) != (G, 2 * inter, H) or tuple(w_down.shape) != (G, H, inter):
+            raise HipOpsError(f"{name}: w_gu {tuple(w_gu.shape)} / w_down {tuple(w_down.shape)} are not "
+                              f"[E + S, 2I, H] / [E + S, H, I] for E {E}, S {n_shared}, H {H}")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not moe_sh_supported(H, inter, E, top_k, n_shared):
+        raise HipOpsError(f"{name}: unsupported shape (hidden {H}, inter {inter}, experts {E}, top_k {top_k}, "
+                          f"shared {n_shared}); see moe_sh_supported")
+    if T * (top_k + n_shared) > MOE_MAX_PAIRS:
+        raise HipOpsError(f"{name}: {T} rows x (top_k {top_k} + shared {n_shared}) exceed {MOE_MAX_PAIRS} pairs per "
+                          f"launch")
+    for t, which in ((w_router, "w_router"), (w_gu, "w_gu"), (w_down, "w_down")):
+        if t is not None and t.device != h.device:
+            raise HipOpsError(f"{name}.{which}: on {t.device}, h is on {h.device}")
+    return T, H, inter, E
+
+
+def moe_route_sig(h: torch.Tensor, w_router: torch.Tensor, bias: torch.Tensor, top_k: int, norm_topk: bool,
+                  route_scale: float = 1.0, n_shared: int = 0) -> tuple:
+    """(ids int32 [T, k + S], p fp32 [T, k + S]): the sigmoid routing kernel of
+    :func:`moe_mlp_sh` alone (dmcp.ops.reference.moe_route_sig_math defines it):
+    the k largest of sigmoid(h . Wr^T) + bias, weighted by the unbiased scores
+    (renormalised over the k when ``norm_topk``, then times ``route_scale``);
+    the last S pairs of a row are the shared pseudo-experts (E + s, 1.0)."""
+    T, H, _, E = _moe_sh_args(h, w_router, bias, None, None, top_k, route_scale, n_shared, "moe_route_sig")
+    kk = top_k + n_shared
+    ids = torch.empty((T, kk), dtype=torch.int32, device=h.device)
+    p = torch.empty((T, kk), dtype=torch.float32, device=h.device)
+    if T:
+        _check(lib().dmcp_moe_route_sig(_ptr(h), _ptr(w_router), _ptr(bias), _ptr(ids), _ptr(p), T, H, E, top_k,
+                                        n_shared, int(bool(norm_topk)), float(route_scale), _stream()),
+               "dmcp_moe_route_sig")
+    return ids, p
+
+
+def moe_mlp_sh(h: torch.Tensor, w_router: torch.Tensor, bias: torch.Tensor, w_gu: torch.Tensor, w_down: torch.Tensor,
+               top_k: int, norm_topk: bool, route_scale: float = 1.0, n_shared: int = 0,
+               residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0,
+               workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`moe_mlp` under the sigmoid router of GLM-4.5 with ``n_shared``
+    shared experts (dmcp.ops.reference.moe_route_sig_math): ``bias`` fp32 [E]
+    enters the selection only; ``w_gu`` [E + S, 2I, H] / ``w_down`` [E + S, H, I]
+    stack the routed experts, then the shared MLP's S slices of width I
+    (dmcp.ops.reference.moe_stack_shared) as pseudo-experts every row chooses
+    with weight 1.  The same six launches over k + S pairs per row and E + S
+    groups -- a shared slice is one group holding all T rows -- capturable, no
+    atomics, the combine in rank order, then slice order.  ``workspace``:
+    :func:`moe_sh_workspace` for at least T rows."""
+    T, H, inter, E = _moe_sh_args(h, w_router, bias, w_gu, w_down, top_k, route_scale, n_shared, "moe_mlp_sh")
+    return _moe_run("moe_mlp_sh", h, w_router, (bias, w_gu, w_down), T, H, inter, E, top_k, norm_topk, residual,
+                    norm_w, eps, workspace, out, shared=(n_shared, float(route_scale)))

@@ -142,13 +142,48 @@ def rope_scaling_key(scaling) -> Optional[tuple]:
     return tuple(sorted([("rope_type", kind)] + [(k, float(d[k])) for k in need]))
 
 
-def rope_inv_freq(head_dim: int, theta: float = 10000.0, scaling=None) -> torch.Tensor:
+def rotary_dim_arg(head_dim: int, rotary_dim: int) -> int:
+    """The rotated width R of a head of ``head_dim``: ``rotary_dim`` 0 means
+    the whole head; else even and in (0, head_dim]."""
+    if isinstance(rotary_dim, bool) or not isinstance(rotary_dim, int) or rotary_dim < 0 or rotary_dim > head_dim \
+            or rotary_dim % 2:
+        raise ValueError(f"rotary_dim {rotary_dim!r} must be 0 (the whole head) or even and in (0, head_dim {head_dim}]")
+    return rotary_dim or head_dim
+
+
+def partial_rotary_perm(head_dim: int, rotary_dim: int) -> torch.Tensor:
+    """Partial rotary embedding on kernels that rotate the whole head.  The
+    checkpoint's code rotates the first R = ``rotary_dim`` dims of a head in
+    half-split pairs (i, i + R/2) and passes dims R .. D-1 through.  The
+    kernels rotate pairs (i, i + D/2) of the whole head.  This index tensor
+    ``perm`` [D] (new[j] = old[perm[j]]) moves pair (i, i + R/2) to
+    (i, i + D/2) and the pass-through dims to the remaining pairs, which
+    :func:`rope_tables` gives frequency 0 (cos 1, sin 0 exactly: unrotated).
+    The loader applies it to each head's rows of q_proj / k_proj (their biases
+    and q_norm / k_norm weights too); the same permutation on q and k leaves
+    every q . k unchanged, so V, o_proj and the attention are untouched."""
+    R = rotary_dim_arg(head_dim, rotary_dim)
+    half, rh = head_dim // 2, R // 2
+    rest = torch.arange(R, head_dim)
+    n1 = half - rh  # pass-through dims in the first half
+    return torch.cat([torch.arange(0, rh), rest[:n1], torch.arange(rh, R), rest[n1:]])
+
+
+def rope_inv_freq(head_dim: int, theta: float = 10000.0, scaling=None, rotary_dim: int = 0) -> torch.Tensor:
     """The rotary pairs' frequencies [D/2] (float64) under ``scaling``: None /
     "default", "linear" (inv_freq / factor) or "llama3" (pairs of wavelength >
     orig / low_freq_factor divided by factor, < orig / high_freq_factor
     unchanged, interpolated between).  The scaling is evaluated in fp32, as
     the checkpoints' own code does, so the frequencies are the ones the model
-    was trained with to the last bit."""
+    was trained with to the last bit.
+
+    ``rotary_dim`` R (0 = the whole head): only R/2 pairs rotate, with the
+    exponent's denominator R, not D; pairs R/2 .. D/2 - 1 get frequency 0
+    (the layout of :func:`partial_rotary_perm`)."""
+    R = rotary_dim_arg(head_dim, rotary_dim)
+    if R != head_dim:
+        inv = rope_inv_freq(R, theta, scaling)
+        return torch.cat([inv, torch.zeros(head_dim // 2 - R // 2, dtype=inv.dtype)])
     half = head_dim // 2
     inv = 1.0 / (theta ** (torch.arange(0, half, dtype=torch.float64) / half))
     sc = dict(rope_scaling_key(scaling) or ())
@@ -169,8 +204,10 @@ def rope_inv_freq(head_dim: int, theta: float = 10000.0, scaling=None) -> torch.
 
 
 def rope_tables(max_pos: int, head_dim: int, theta: float = 10000.0, device=None, scaling=None,
-                fp32_angles: bool = False) -> torch.Tensor:
+                fp32_angles: bool = False, rotary_dim: int = 0) -> torch.Tensor:
     """[max_pos, D/2, 2] float32 (cos, sin) -- viewed as float2 by the kernel.
+    ``rotary_dim`` (0 = the whole head): see :func:`rope_inv_freq`; the
+    pass-through pairs' rows are cos 1, sin 0 exactly.
     ``scaling``: a ``rope_scaling`` dict (or its :func:`rope_scaling_key`
     form) of type "linear" or "llama3"; None = the plain ``theta`` table.
     ``fp32_angles``: frequencies, angles and cos / sin in fp32, the way the
@@ -178,6 +215,12 @@ def rope_tables(max_pos: int, head_dim: int, theta: float = 10000.0, device=None
     up to 3e-5 rad at position 1,000).  QK-norm models use it: their unit-RMS
     q / k turn that angle rounding into attention-logit differences ~40x the
     fp32 noise of an un-normed model (tests/test_checkpoint_qwen3.py)."""
+    R = rotary_dim_arg(head_dim, rotary_dim)
+    if R != head_dim:
+        t = rope_tables(max_pos, R, theta, None, scaling, fp32_angles)
+        rest = torch.zeros((max_pos, head_dim // 2 - R // 2, 2), dtype=t.dtype)
+        rest[..., 0] = 1.0
+        return torch.cat([t, rest], dim=1).to(device)
     if fp32_angles:
         half = head_dim // 2
         if rope_scaling_key(scaling) is None:
@@ -1103,6 +1146,150 @@ def moe_mlp(h: torch.Tensor, w_router: torch.Tensor, w_gu: torch.Tensor, w_down:
     _moe_check(h, w_router, w_gu, w_down, top_k, "moe_mlp")
     m = moe_mlp_math(h.float(), w_router.float(), w_gu.float(), w_down.float(), int(top_k), bool(norm_topk),
                      round_act=lambda a: a.to(torch.bfloat16).float()).to(h.dtype)
+    if norm_w is not None:
+        return add_rmsnorm(m, norm_w, eps, residual=residual, out=out)
+    if residual is not None:
+        residual.copy_((m.float() + residual.float()).to(residual.dtype))
+        return residual
+    if out is not None:
+        out.copy_(m)
+        return out
+    return m
+
+
+# ---- sigmoid routing with shared experts (GLM-4.5, ``glm4_moe``; the router
+# of DeepSeek-V3-style blocks with one expert group).  For each row of h:
+#
+#   s      = sigmoid(h . Wr^T)                          over E experts
+#   chosen = the k largest of s + bias (bias fp32 [E], ``e_score_correction_bias``:
+#            it enters the selection only); a tie goes to the lower expert id
+#   weight = the unbiased s of the chosen experts, divided by (sum + 1e-20)
+#            when norm_topk, then multiplied by route_scale
+#   y      = sum_j weight_j * expert_{chosen_j}(h) + shared(h)
+#
+# where shared is an always-on SwiGLU MLP of width S * I (S = n_shared).  A NaN
+# logit never wins and never blocks the selection (its selection score is
+# -inf, its weight 0).
+#
+# A SwiGLU MLP is a sum over slices of its intermediate dimension:
+#   down(silu(gate(h)) * up(h)) = sum_s down[:, sI:(s+1)I] (silu(gate[sI:(s+1)I] h) * up[sI:(s+1)I] h)
+# so a shared MLP of width S * I is exactly S always-chosen experts of width I
+# with weight 1.  The ops take it that way: w_gu [E + S, 2 I, H] and w_down
+# [E + S, H, I] stack the E routed experts, then the S slices
+# (:func:`moe_stack_shared`), and a row has k + S (expert, weight) pairs -- its
+# k routed ones in rank order, then (E + s, 1.0) for s = 0 .. S - 1.
+def moe_route_sig_math(h: torch.Tensor, w_router: torch.Tensor, bias: torch.Tensor, top_k: int, norm_topk: bool,
+                       route_scale: float = 1.0, n_shared: int = 0) -> tuple:
+    """(ids int64 [T, k + S], p [T, k + S]) in the dtype of ``h`` (fp32 or
+    fp64): the definition above, shared by the bf16 op, the model's fp32
+    reference forward and the tests' fp64 oracle."""
+    E = w_router.shape[0]
+    if not 1 <= top_k <= E:
+        raise ValueError(f"moe_route_sig: top_k {top_k} outside [1, {E}] (num_experts)")
+    if n_shared < 0:
+        raise ValueError(f"moe_route_sig: n_shared {n_shared} is negative")
+    logits = h @ w_router.t()
+    bad = logits.isnan()
+    s = torch.where(bad, torch.zeros_like(logits), torch.sigmoid(logits))
+    choice = s + bias.to(s.dtype)
+    choice = torch.where(bad | choice.isnan(), torch.full_like(choice, float("-inf")), choice)
+    # a stable descending sort keeps the lower id first among equal scores
+    order = torch.sort(choice, dim=-1, descending=True, stable=True).indices[:, :top_k]
+    p = s.gather(1, order)
+    if norm_topk:
+        p = p / (p.sum(-1, keepdim=True) + 1e-20)
+    p = p * route_scale
+    if n_shared:
+        T = h.shape[0]
+        order = torch.cat([order, (E + torch.arange(n_shared, device=order.device)).expand(T, n_shared)], 1)
+        p = torch.cat([p, torch.ones((T, n_shared), dtype=p.dtype, device=p.device)], 1)
+    return order, p
+
+
+def moe_stack_shared(w_gu: torch.Tensor, w_down: torch.Tensor, sh_gate: Optional[torch.Tensor],
+                     sh_up: Optional[torch.Tensor], sh_down: Optional[torch.Tensor], n_shared: int) -> tuple:
+    """(w_gu [E + S, 2I, H], w_down [E + S, H, I]): the routed stacks with the
+    shared MLP (gate / up [S I, H], down [H, S I]) appended as S slices of
+    width I: slice s takes gate rows [sI, (s+1)I), the same up rows and down
+    columns [sI, (s+1)I)."""
+    if not n_shared:
+        return w_gu, w_down
+    E, H, inter = w_down.shape
+    if tuple(sh_gate.shape) != (n_shared * inter, H) or tuple(sh_up.shape) != (n_shared * inter, H) \
+            or tuple(sh_down.shape) != (H, n_shared * inter):
+        raise ValueError(f"moe_stack_shared: shared gate {tuple(sh_gate.shape)} / up {tuple(sh_up.shape)} / down "
+                         f"{tuple(sh_down.shape)} are not [S I, H] / [S I, H] / [H, S I] for S {n_shared}, I {inter}, "
+                         f"H {H}")
+    gu = torch.cat([sh_gate.view(n_shared, inter, H), sh_up.view(n_shared, inter, H)], 1)
+    down = sh_down.view(H, n_shared, inter).permute(1, 0, 2)
+    return torch.cat([w_gu, gu.to(w_gu.dtype)], 0).contiguous(), torch.cat([w_down, down.to(w_down.dtype)], 0).contiguous()
+
+
+def moe_mlp_sh_math(h: torch.Tensor, w_router: torch.Tensor, bias: torch.Tensor, w_gu: torch.Tensor,
+                    w_down: torch.Tensor, top_k: int, norm_topk: bool, route_scale: float = 1.0, n_shared: int = 0,
+                    round_act=None) -> torch.Tensor:
+    """y [T, H] in the dtype of ``h`` (fp32 or fp64; weights of that dtype):
+    the routed ranks in rank order, then the shared slices in order.
+    ``round_act``: applied to silu(gate) * up (the kernel keeps it in bf16)."""
+    ids, p = moe_route_sig_math(h, w_router, bias, top_k, norm_topk, route_scale, n_shared)
+    inter = w_down.shape[2]
+    y = torch.zeros_like(h)
+    for j in range(top_k + n_shared):
+        for e in ids[:, j].unique().tolist():
+            rows = (ids[:, j] == e).nonzero()[:, 0]
+            x = h[rows]
+            gu = x @ w_gu[e].t()
+            g, u = gu[:, :inter], gu[:, inter:]
+            act = g / (1.0 + torch.exp(-g)) * u
+            if round_act is not None:
+                act = round_act(act)
+            y[rows] += p[rows, j:j + 1] * (act @ w_down[e].t())
+    return y
+
+
+def _moe_sh_check(h, w_router, bias, w_gu, w_down, top_k, route_scale, n_shared, name):
+    E, H = w_router.shape
+    if h.dim() != 2 or h.shape[1] != H:
+        raise ValueError(f"{name}: h {tuple(h.shape)} does not match the router {tuple(w_router.shape)}")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= E:
+        raise ValueError(f"{name}: top_k {top_k} outside [1, {E}] (num_experts)")
+    if isinstance(n_shared, bool) or not isinstance(n_shared, int) or n_shared < 0:
+        raise ValueError(f"{name}: n_shared {n_shared!r} must be an integer >= 0")
+    if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (E,):
+        raise ValueError(f"{name}: bias must be fp32 [{E}], got "
+                         f"{getattr(bias, 'dtype', type(bias).__name__)} {tuple(getattr(bias, 'shape', ()))}")
+    if not (math.isfinite(route_scale) and route_scale > 0):
+        raise ValueError(f"{name}: route_scale {route_scale!r} must be finite and > 0")
+    if w_gu is not None:
+        G = E + n_shared
+        inter = w_down.shape[2] if w_down.dim() == 3 else -1
+        if tuple(w_gu.shape) != (G, 2 * inter, H) or tuple(w_down.shape) != (G, H, inter):
+            raise ValueError(f"{name}: w_gu {tuple(w_gu.shape)} / w_down {tuple(w_down.shape)} are not "
+                             f"[E + S, 2I, H] / [E + S, H, I] for E {E}, S {n_shared}, H {H}")
+
+
+def moe_route_sig(h: torch.Tensor, w_router: torch.Tensor, bias: torch.Tensor, top_k: int, norm_topk: bool,
+                  route_scale: float = 1.0, n_shared: int = 0) -> tuple:
+    """(ids int32 [T, k + S], p fp32 [T, k + S]) of bf16 rows ``h`` [T, H]
+    under the bf16 router ``w_router`` [E, H] and the fp32 selection bias [E]:
+    logits, sigmoid and selection in fp32."""
+    _moe_sh_check(h, w_router, bias, None, None, top_k, route_scale, n_shared, "moe_route_sig")
+    ids, p = moe_route_sig_math(h.float(), w_router.float(), bias, int(top_k), bool(norm_topk), float(route_scale),
+                                int(n_shared))
+    return ids.to(torch.int32), p
+
+
+def moe_mlp_sh(h: torch.Tensor, w_router: torch.Tensor, bias: torch.Tensor, w_gu: torch.Tensor, w_down: torch.Tensor,
+               top_k: int, norm_topk: bool, route_scale: float = 1.0, n_shared: int = 0,
+               residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0,
+               workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`moe_mlp` under the sigmoid router with ``n_shared`` shared
+    pseudo-experts stacked after the routed ones (the definition above);
+    residual / norm_w / out as there."""
+    _moe_sh_check(h, w_router, bias, w_gu, w_down, top_k, route_scale, n_shared, "moe_mlp_sh")
+    m = moe_mlp_sh_math(h.float(), w_router.float(), bias, w_gu.float(), w_down.float(), int(top_k), bool(norm_topk),
+                        float(route_scale), int(n_shared),
+                        round_act=lambda a: a.to(torch.bfloat16).float()).to(h.dtype)
     if norm_w is not None:
         return add_rmsnorm(m, norm_w, eps, residual=residual, out=out)
     if residual is not None:

@@ -637,6 +637,92 @@ def qwen3_moe_checkpoint(root: str, n_experts: int = 8, experts_per_tok: int = 2
     return root
 
 
+def glm4_moe_checkpoint(root: str, n_experts: int = 8, experts_per_tok: int = 2, moe_intermediate: int = 128,
+                        n_shared: int = 1, dense_lead: int = 1, norm_topk: bool = True, route_scale: float = 1.0,
+                        partial_rotary: Optional[float] = 0.5, rotary_in_rope_parameters: bool = False,
+                        qk_norm: bool = False, qkv_bias: bool = True, mtp_layers: int = 0, bias_std: float = 0.5,
+                        seed: int = 11, device: str = "cuda", **kw) -> str:
+    """A GLM-4.5 checkpoint directory (``model_type: glm4_moe``) in the hub
+    layout: what :func:`llama_checkpoint` writes (``kw`` goes there: geometry,
+    tokenizer, tied embeddings, ...; q/k/v biases with ``qkv_bias``, per-head
+    q/k norms with ``qk_norm``) where layers ``dense_lead ..`` replace the dense
+    MLP by a router ``mlp.gate.weight`` [E, hidden], its fp32 selection bias
+    ``mlp.gate.e_score_correction_bias`` [E], ``mlp.experts.{e}.*`` and -- with
+    ``n_shared`` > 0 -- ``mlp.shared_experts.{gate,up,down}_proj.weight`` of
+    width ``n_shared * moe_intermediate``, all drawn from a generator of their
+    own.  The router is drawn as :func:`qwen3_moe_checkpoint`'s; the bias at
+    ``bias_std`` 0.5, more than the spread of the sigmoid scores themselves, so it
+    changes the chosen experts on a large share of the rows (a loader that
+    dropped it cannot pass).  ``route_scale``: ``routed_scaling_factor``.
+    ``partial_rotary``: ``partial_rotary_factor`` (None: the key is absent and
+    the model type's 0.5 applies), written at the top level or, with
+    ``rotary_in_rope_parameters``, inside ``rope_parameters``.  ``mtp_layers``:
+    that many whole extra layers after the last one (the multi-token-prediction
+    layers of the hub files, with their ``eh_proj`` / ``enorm`` / ``hnorm`` /
+    ``shared_head`` tensors) and ``num_nextn_predict_layers``."""
+    import json
+
+    import torch
+    from safetensors.torch import load_file, save_file
+    llama_checkpoint(root, seed=seed, device=device, qkv_bias=qkv_bias, qk_norm=qk_norm, **kw)
+    f = os.path.join(root, "model.safetensors")
+    t = load_file(f)
+    with open(os.path.join(root, "config.json")) as fh:
+        cfg = json.load(fh)
+    hidden, layers = cfg["hidden_size"], cfg["num_hidden_layers"]
+    g = torch.Generator(device=device).manual_seed(seed + 2000)
+
+    def rnd(shape, std, dtype=torch.bfloat16):
+        return (torch.randn(shape, generator=g, device=device) * std).to(dtype).cpu()
+    out_std = 0.02 / (2 * layers) ** 0.5
+
+    def sparse(p):
+        for n in ("gate_proj", "up_proj", "down_proj"):
+            t.pop(p + n + ".weight", None)
+        t[p + "gate.weight"] = rnd((n_experts, hidden), 2.0 / hidden ** 0.5)
+        t[p + "gate.e_score_correction_bias"] = rnd((n_experts,), bias_std, torch.float32)
+        for e in range(n_experts):
+            t[f"{p}experts.{e}.gate_proj.weight"] = rnd((moe_intermediate, hidden), 0.02)
+            t[f"{p}experts.{e}.up_proj.weight"] = rnd((moe_intermediate, hidden), 0.02)
+            t[f"{p}experts.{e}.down_proj.weight"] = rnd((hidden, moe_intermediate), out_std)
+        if n_shared:
+            w = n_shared * moe_intermediate
+            t[p + "shared_experts.gate_proj.weight"] = rnd((w, hidden), 0.02)
+            t[p + "shared_experts.up_proj.weight"] = rnd((w, hidden), 0.02)
+            t[p + "shared_experts.down_proj.weight"] = rnd((hidden, w), out_std)
+    for i in range(dense_lead, layers):
+        sparse(f"model.layers.{i}.mlp.")
+    for i in range(layers, layers + mtp_layers):  # a copy of the last layer's attention, a routed MLP, the MTP extras
+        p = f"model.layers.{i}."
+        for n in [n for n in t if n.startswith(f"model.layers.{layers - 1}.") and ".mlp." not in n]:
+            t[p + n.split(".", 3)[3]] = t[n].clone()
+        sparse(p + "mlp.")
+        t[p + "eh_proj.weight"] = rnd((hidden, 2 * hidden), 0.02)
+        t[p + "enorm.weight"] = torch.ones(hidden, dtype=torch.bfloat16)
+        t[p + "hnorm.weight"] = torch.ones(hidden, dtype=torch.bfloat16)
+        t[p + "shared_head.norm.weight"] = torch.ones(hidden, dtype=torch.bfloat16)
+    save_file(t, f)
+    hd = cfg.get("head_dim") or hidden // cfg["num_attention_heads"]
+    cfg.pop("rope_scaling", None)
+    cfg.update({"model_type": "glm4_moe", "architectures": ["Glm4MoeForCausalLM"], "hidden_act": "silu",
+                "head_dim": hd, "attention_bias": bool(qkv_bias), "use_qk_norm": bool(qk_norm),
+                "n_routed_experts": n_experts, "num_experts_per_tok": experts_per_tok,
+                "moe_intermediate_size": moe_intermediate, "n_shared_experts": n_shared,
+                "first_k_dense_replace": dense_lead, "norm_topk_prob": bool(norm_topk),
+                "routed_scaling_factor": route_scale, "n_group": 1, "topk_group": 1,
+                "num_nextn_predict_layers": mtp_layers, "attention_dropout": 0.0, "rope_theta": 1000000.0,
+                "max_position_embeddings": 4096})
+    if partial_rotary is not None:
+        if rotary_in_rope_parameters:
+            cfg["rope_parameters"] = {"rope_type": "default", "rope_theta": cfg.pop("rope_theta"),
+                                      "partial_rotary_factor": partial_rotary}
+        else:
+            cfg["partial_rotary_factor"] = partial_rotary
+    with open(os.path.join(root, "config.json"), "w") as fh:
+        json.dump(cfg, fh)
+    return root
+
+
 def write_chat_template(root: str, chat_template: str, vocab: int) -> Optional[int]:
     """Makes the tokenizer of the checkpoint directory ``root`` an instruct
     model's: every ``<|...|>`` marker of ``chat_template`` becomes a special
